@@ -13,6 +13,13 @@ pass of the fused join+aggregate over the rank's resident shard (inputs
 already in HBM) + the cross-rank partial-aggregate merge + the
 result read.
 
+A plain run does only what the headline figure needs: setup, warmup, the K
+timed steps, the result line. `--full` adds everything else the line can
+carry — the kernel-only roofline pass (HIP events + committed PMC traffic) and
+the CPU-oracle baseline — which take runs of their own. `--dump-outputs DIR`
+writes what the last timed step returned to its caller as DIR/<name>.npy
+(float64; inputs are seeded, so two builds compare output for output).
+
 Workloads: q21 (default, config 3), q1 (config 2), q43 (config 4 — at N>1 it
 runs the MANDATED hash-partitioned mode: per-step partition kernel + gather +
 RCCL all-to-all of the probe columns on lo_custkey, then local probe+agg).
@@ -40,6 +47,7 @@ Q3_N_ORDERS, Q3_N_CUSTS = 450_000_000, 45_000_000  # SF300
 Q3_ROWS_PER_GPU = 225_000_000  # 8 GPUs × 225 M = the §8d 1.8 B-row dataset
 Q3_CUTOFF = 19950315
 HBM_PEAK_GBPS = 8000.0       # 8 TB/s spec peak (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs budget (stays under 64 MB with headers)
 
 
 def log(msg):
@@ -257,6 +265,21 @@ def read_pmc_traffic(workload, rows, world):
     return None
 
 
+def dump_outputs(dirpath, arrays):
+    """Write {name: array} as dirpath/<name>.npy in float64 (every value here
+    is an integer below 2^53, so the cast is exact). Arrays that would push
+    the dump past DUMP_MAX_BYTES are cut to a fixed seeded sample of their
+    elements — the same indices for equal-length arrays, so sampled keys and
+    sums stay aligned."""
+    os.makedirs(dirpath, exist_ok=True)
+    cap = DUMP_MAX_BYTES // len(arrays) // 8
+    for name, a in arrays.items():
+        a = np.asarray(a).ravel()
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(SEED).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(dirpath, name + ".npy"), a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -264,7 +287,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", choices=["q1", "q21", "q43", "q3"], default="q21")
     ap.add_argument("--rows", type=int, default=0, help="override rows per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the kernel-only roofline pass and the CPU-oracle "
+                         "baseline (separate runs after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result arrays to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", args.gpus))
     rank = int(os.environ.get("RANK", 0))
@@ -679,7 +709,7 @@ def main():
     eng.sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run_step()
+        out = run_step()
     eng.sync()
     if dist is not None:
         torch.cuda.synchronize()
@@ -694,35 +724,53 @@ def main():
     value = rows * world * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000
 
-    # ---- roofline evidence: HIP events around kernel-only launches ----
-    R = 20
-    eng.sync()
-    eng.timer_start()
-    for _ in range(R):
-        kernel_only()
-    kernel_ms = eng.timer_stop() / R
-    kernel_rows = rows if not (wl in ("q43", "q3") and world > 1) else max(n_recv, 1)
-    algo_bytes = BYTES_PER_ROW[wl] * kernel_rows
-    achieved_gbps = algo_bytes / (kernel_ms / 1e3) / 1e9
-    traffic = read_pmc_traffic(wl, rows, world)
-    # Honest presentation: `achieved`/`frac` are
-    # kernel-only HIP-event timing of ALGORITHMIC bytes; `achieved_step`/
-    # `frac_step` divide the same bytes by the full step (incl. result read);
-    # `frac_physical` uses the PMC-counted bytes actually moved (q43's
-    # deferred loads fetch FEWER than algorithmic; q3 fetches more).
-    step_gbps = BYTES_PER_ROW[wl] * rows / (ms_per_step / 1e3) / 1e9
-    roofline = {"bound": "hbm", "achieved": round(achieved_gbps, 1), "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s", "frac": round(achieved_gbps / HBM_PEAK_GBPS, 4),
-                "achieved_step": round(step_gbps, 1),
-                "frac_step": round(step_gbps / HBM_PEAK_GBPS, 4),
-                "frac_physical": (round(traffic / (kernel_ms / 1e3) / 1e9
-                                        / HBM_PEAK_GBPS, 4) if traffic else None),
-                "traffic": traffic}
+    # ---- --dump-outputs: what the last timed step handed its caller ----
+    if args.dump_outputs and rank == 0:
+        if wl == "q3":
+            # the step returns the group count; the groups themselves sit in
+            # the emit buffers in hash-table order — sorted by key here so
+            # two runs line up
+            g = int(out[0])
+            keys = ok_b.d2h(np.uint64, g)
+            order = np.argsort(keys, kind="stable")
+            arrays = {"q3_n_groups": out, "q3_group_keys": keys[order],
+                      "q3_group_sums": os_b.d2h(np.int64, g)[order]}
+        else:
+            arrays = {{"q1": "q1_sum_count", "q21": "q21_group_sums",
+                       "q43": "q43_group_sums"}[wl]: out}
+        dump_outputs(args.dump_outputs, arrays)
+
+    roofline = None
+    if args.full:
+        # ---- roofline evidence: HIP events around kernel-only launches ----
+        R = 20
+        eng.sync()
+        eng.timer_start()
+        for _ in range(R):
+            kernel_only()
+        kernel_ms = eng.timer_stop() / R
+        kernel_rows = rows if not (wl in ("q43", "q3") and world > 1) else max(n_recv, 1)
+        algo_bytes = BYTES_PER_ROW[wl] * kernel_rows
+        achieved_gbps = algo_bytes / (kernel_ms / 1e3) / 1e9
+        traffic = read_pmc_traffic(wl, rows, world)
+        # Honest presentation: `achieved`/`frac` are
+        # kernel-only HIP-event timing of ALGORITHMIC bytes; `achieved_step`/
+        # `frac_step` divide the same bytes by the full step (incl. result read);
+        # `frac_physical` uses the PMC-counted bytes actually moved (q43's
+        # deferred loads fetch FEWER than algorithmic; q3 fetches more).
+        step_gbps = BYTES_PER_ROW[wl] * rows / (ms_per_step / 1e3) / 1e9
+        roofline = {"bound": "hbm", "achieved": round(achieved_gbps, 1), "peak": HBM_PEAK_GBPS,
+                    "unit": "GB/s", "frac": round(achieved_gbps / HBM_PEAK_GBPS, 4),
+                    "achieved_step": round(step_gbps, 1),
+                    "frac_step": round(step_gbps / HBM_PEAK_GBPS, 4),
+                    "frac_physical": (round(traffic / (kernel_ms / 1e3) / 1e9
+                                            / HBM_PEAK_GBPS, 4) if traffic else None),
+                    "traffic": traffic}
 
     if rank == 0:
-        # GPUE_SKIP_CPU_BASELINE=1: omit the ~10 s oracle leg during kernel
-        # sweeps; the driver's default run always measures it
-        if os.environ.get("GPUE_SKIP_CPU_BASELINE") == "1":
+        # CPU-oracle baseline: --full only (it is ~10 s of host work);
+        # GPUE_SKIP_CPU_BASELINE=1 omits it there too, for kernel sweeps
+        if not args.full or os.environ.get("GPUE_SKIP_CPU_BASELINE") == "1":
             cb = None
         else:
             cb = cpu_baseline(wl, rows) if world == 1 and wl != "q3" else (
