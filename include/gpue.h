@@ -413,7 +413,13 @@ int gpue_q21_star_agg(gpue_session* s, gpue_join_table* parts, gpue_join_table* 
 /* Two-stream pipelined variant: K_A (part runtime-filter probe + brand
  * payload -> u16 per row, brand_scratch) overlaps K_B (remaining streams +
  * supplier/date probes + group agg) across n_chunks chunks — the two legs
- * measured fully additive inside one kernel. */
+ * measured fully additive inside one kernel.
+ * Rows are split into n_chunks chunks of ceil(n_rows / n_chunks) rows rounded
+ * up to a multiple of 4; trailing empty chunks launch nothing and n_rows == 0
+ * returns zeros. brand_scratch is written on the session's second stream
+ * while the session stream still reads it, and it is reused across calls:
+ * the caller must gpue_sync() before passing the same brand_scratch to a
+ * second pipe call (or freeing it). */
 int gpue_q21_star_agg_pipe(gpue_session* s, gpue_join_table* parts, gpue_join_table* supps,
                            gpue_join_table* dates, gpue_dbuf* lo_partkey, gpue_dbuf* lo_suppkey,
                            gpue_dbuf* lo_orderdate, gpue_dbuf* lo_revenue, uint64_t n_rows,

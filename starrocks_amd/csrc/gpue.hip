@@ -4841,10 +4841,15 @@ int gpue_q21_star_agg_pipe(gpue_session* s, gpue_join_table* parts, gpue_join_ta
     ARG_CHECK(brand_scratch->bytes >= n * 2);
     ARG_CHECK(n_chunks >= 1 && n_chunks <= gpue_session::N_CHUNK_EVENTS);
     HIP_CHECK(hipMemsetAsync(group_sums->ptr, 0, NG_Q21 * sizeof(int64_t), s->stream));
-    uint64_t chunk = ((n / n_chunks) + 3) & ~3ull; // 4-row aligned chunks
+    // 4-row-aligned CEILING of n / n_chunks: n_chunks chunks then cover every
+    // row (a floor here drops up to n_chunks-1 trailing rows whenever
+    // n / n_chunks is already a multiple of 4) and every chunk start stays
+    // 16-byte aligned for the int4 column loads
+    uint64_t per = (n + (uint64_t)n_chunks - 1) / (uint64_t)n_chunks;
+    uint64_t chunk = (per + 3) & ~3ull;
     for (int c = 0; c < n_chunks; c++) {
         uint64_t lo = (uint64_t)c * chunk;
-        if (lo >= n) break;
+        if (lo >= n) break; // trailing chunks are empty (also n == 0): no launch
         uint64_t len = min(chunk, n - lo);
         hipLaunchKernelGGL(k_q21_pass_payload, dim3(grid_for(len)), dim3(BLOCK), 0,
                            s->stream2, (const int32_t*)pk->ptr + lo, len, parts->bitset,
