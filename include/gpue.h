@@ -570,6 +570,38 @@ int gpue_page_decode_bshuf_lz4_i32(gpue_session* s, gpue_dbuf* page, uint32_t n_
  * deterministic (value, key) lexicographic descending; k <= 16. */
 int gpue_topk_i64(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* vals, uint64_t n,
                   int k, uint64_t* out_keys, int64_t* out_vals);
+/* General TopN: multi-key ORDER BY ... LIMIT/OFFSET for any k — the
+ * ChunksSorterTopn result (reference exec/chunks_sorter_topn.cpp) under the
+ * reference's SortDesc (per-key sort direction + null placement,
+ * exec/sorting/sorting.h SortDesc/SortDescs). Output = positions
+ * [offset, offset+limit) of the total order of all n_rows rows, as u32 row
+ * indices in result order; out_count = min(limit, max(n_rows - offset, 0)).
+ * Order: lexicographic over the keys, each ascending or descending by its
+ * flag; a NULL row sorts before every non-NULL value of that key under
+ * NULLS_FIRST, after under NULLS_LAST, whatever the direction; the stored
+ * value of a NULL row is never read into the order. Rows equal on every key
+ * (two NULLs of one key included) come out in ascending row index — the
+ * reference leaves that order unspecified; pinning it makes the result equal
+ * a stable sort. Payload columns are materialized by the caller with
+ * gpue_gather_u32/u64 over out_row_idx. GPUE_ERR_ARG (before any launch)
+ * for n_keys outside 1..8, an unknown key type, n_rows >= 2^32, a key/null
+ * buffer shorter than n_rows elements, or out_row_idx shorter than
+ * out_count*4 bytes; n_rows == 0, limit == 0 and offset >= n_rows return
+ * GPUE_OK with count 0. key_nulls may itself be NULL (no nullable key). */
+#define GPUE_TOPN_I32 0
+#define GPUE_TOPN_I64 1
+#define GPUE_TOPN_U64 2
+#define GPUE_TOPN_DESC 1        /* key_flags bit 0 */
+#define GPUE_TOPN_NULLS_FIRST 2 /* key_flags bit 1 */
+int gpue_topn(gpue_session* s,
+              gpue_dbuf** key_cols,      /* n_keys sort columns, most significant first */
+              gpue_dbuf** key_nulls,     /* n_keys entries; each NULL or a u8 mask, nonzero = NULL row */
+              const int32_t* key_type,   /* GPUE_TOPN_I32 / _I64 / _U64 */
+              const int32_t* key_flags,  /* GPUE_TOPN_DESC | GPUE_TOPN_NULLS_FIRST */
+              int n_keys, uint64_t n_rows,
+              uint64_t offset, uint64_t limit,
+              gpue_dbuf* out_row_idx,    /* u32 row indices, in result order */
+              uint64_t* out_count);
 
 /* ---- chunked-exchange overlap support (SURVEY.md §7 hard part (d)) ------
  * The session's HIP stream as an opaque pointer (wrap as a torch

@@ -8700,6 +8700,668 @@ int gpue_topk_i64(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* vals, uint64_t n,
 }
 
 // ---------------------------------------------------------------------------
+// General TopN — multi-key ORDER BY ... LIMIT/OFFSET for any k (reference
+// exec/chunks_sorter_topn.cpp; per-key direction and null placement as the
+// reference's SortDesc, exec/sorting/sorting.h). Nothing here is sized by k.
+//
+// Each key normalizes to (class, v): class 0 = NULL under NULLS_FIRST,
+// 1 = non-NULL, 2 = NULL under NULLS_LAST; v = order-preserving unsigned
+// image of the value (sign bit flipped for signed types, all bits inverted
+// for DESC, 0 for NULL rows so stored garbage never matters).
+//
+// Select (MSD radix-select, key by key, K = offset+limit):
+//   class pass  : 3-bin histogram of the candidates' class + min/max of v
+//                 over the non-NULL ones — the min/max common prefix is
+//                 skipped, so the first digit always narrows;
+//   digit passes: TOPN_RBITS-bit digits of v from the first varying bit
+//                 down; per-block LDS histogram -> global histogram;
+//   plan        : one block finds the pivot bin on device and scans the
+//                 per-block pivot counts into write offsets;
+//   compact     : rows before the pivot bin are definite winners (appended
+//                 through one cursor, order irrelevant), rows on it stay
+//                 candidates through an ORDERED compaction (ascending row
+//                 order is what makes "digits ran out -> take the first R"
+//                 a stable tie-break), the rest are dropped.
+// The host reads back only the plan's 32-byte result per pass (loop control
+// + buffer sizing). Selection stops when the candidates equal what remains
+// of K, when winners+candidates fit one LDS sort tile, or when the keys run
+// out. K >= n_rows (full ORDER BY) and n_rows <= one tile skip selection.
+//
+// Sort: the >= K survivors are ordered by the full comparator (all keys,
+// row index last) — bitonic over (k0, row) pairs where k0 is a monotone
+// 64-bit coarsening of key 0 that decides most compares without a gather;
+// one LDS tile per block for strides inside a tile, one launch per stride
+// beyond it. Then positions [offset, K) are copied out.
+// ---------------------------------------------------------------------------
+static constexpr int TOPN_MAX_KEYS = 8;
+static constexpr int TOPN_RBITS = 11;
+static constexpr uint32_t TOPN_NB = 1u << TOPN_RBITS;      // 8 KB LDS histogram
+static constexpr int TOPN_ITEMS = 8;
+static constexpr uint32_t TOPN_TILE = BLOCK * TOPN_ITEMS;  // compaction tile (rows)
+// select grid = 4 blocks/CU: measured 0.68 ms at 1024 blocks vs 0.86 at 512,
+// 1.31 at 256 and 0.72 at 2048 (64 Mi rows, k = 10) — the select passes are
+// latency-bound streams that want the waves, while every extra block adds an
+// 8 KB histogram to write and merge
+static constexpr uint32_t TOPN_MAX_BLOCKS = 1024;
+static constexpr uint32_t TOPN_SORT_TILE = 4096;           // 48 KB LDS: 3 blocks/CU
+static constexpr int TOPN_SORT_TPB = 512;
+static constexpr uint32_t TOPN_PAD_ROW = 0xFFFFFFFFu;      // n_rows < 2^32: never a row
+
+struct TopnKeys {
+    const void* col[TOPN_MAX_KEYS];
+    const uint8_t* nulls[TOPN_MAX_KEYS];
+    int32_t type[TOPN_MAX_KEYS];
+    int32_t flags[TOPN_MAX_KEYS];
+    int32_t n_keys;
+};
+
+struct TopnState {
+    unsigned long long nvmin, vmax; // class-pass accumulators (nvmin = ~min)
+    unsigned int win_cursor, pad0;
+    // plan result — the 32 bytes the host reads back per pass
+    unsigned long long r_vmin, r_vmax;
+    unsigned int r_pivot, r_before, r_npivot, pad1;
+    unsigned int blk_off[TOPN_MAX_BLOCKS];
+    unsigned int hist[TOPN_NB];
+};
+
+__device__ static inline uint64_t topn_norm_raw(uint64_t raw, int type, int flags) {
+    uint64_t x;
+    if (type == 0) {
+        uint32_t u = (uint32_t)raw ^ 0x80000000u;
+        x = (flags & 1) ? (uint64_t)(~u) : (uint64_t)u;
+    } else {
+        x = raw;
+        if (type == 1) x ^= 1ull << 63;
+        if (flags & 1) x = ~x;
+    }
+    return x;
+}
+
+__device__ static inline uint64_t topn_norm(const void* col, int type, int flags,
+                                            uint32_t row) {
+    uint64_t raw = type == 0 ? (uint64_t)((const uint32_t*)col)[row]
+                             : ((const uint64_t*)col)[row];
+    return topn_norm_raw(raw, type, flags);
+}
+
+static constexpr uint32_t TOPN_CLS_NONE = 3u; // position past the block's range
+
+// One striped tile of a select pass: item j of thread t is candidate position
+// tb + j*BLOCK + t, so every load instruction is coalesced. Positions are
+// clamped instead of branched on, so the TOPN_ITEMS loads of each stage
+// (candidate list, null mask, value) issue back to back and a thread keeps
+// that many requests in flight. Reading a NULL row's stored value is legal
+// (the buffer holds n_rows elements); it is discarded here.
+__device__ static inline void topn_tile_load(const void* __restrict__ col,
+                                             const uint8_t* __restrict__ nulls, int type,
+                                             int flags, const uint32_t* __restrict__ cand,
+                                             uint64_t tb, uint64_t p1,
+                                             uint32_t (&row)[TOPN_ITEMS],
+                                             uint32_t (&cls)[TOPN_ITEMS],
+                                             uint64_t (&v)[TOPN_ITEMS]) {
+    uint64_t raw[TOPN_ITEMS];
+    uint32_t nb[TOPN_ITEMS];
+#pragma unroll
+    for (int j = 0; j < TOPN_ITEMS; j++) {
+        uint64_t pos = tb + (uint64_t)j * BLOCK + threadIdx.x;
+        uint64_t pc = pos < p1 ? pos : p1 - 1;
+        row[j] = cand ? cand[pc] : (uint32_t)pc;
+    }
+    if (type == 0) {
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++) raw[j] = ((const uint32_t*)col)[row[j]];
+    } else {
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++) raw[j] = ((const uint64_t*)col)[row[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < TOPN_ITEMS; j++) nb[j] = nulls ? nulls[row[j]] : 0u;
+#pragma unroll
+    for (int j = 0; j < TOPN_ITEMS; j++) {
+        uint64_t pos = tb + (uint64_t)j * BLOCK + threadIdx.x;
+        if (pos >= p1) {
+            cls[j] = TOPN_CLS_NONE;
+            v[j] = 0;
+        } else if (nb[j]) {
+            cls[j] = (flags & 2) ? 0u : 2u;
+            v[j] = 0;
+        } else {
+            cls[j] = 1u;
+            v[j] = topn_norm_raw(raw[j], type, flags);
+        }
+    }
+}
+
+__device__ static inline void topn_load(const void* col, const uint8_t* nulls, int type,
+                                        int flags, uint32_t row, uint32_t& cls,
+                                        uint64_t& v) {
+    if (nulls && nulls[row]) {
+        cls = (flags & 2) ? 0u : 2u;
+        v = 0;
+    } else {
+        cls = 1u;
+        v = topn_norm(col, type, flags, row);
+    }
+}
+
+// full comparator: all keys, row index last; TOPN_PAD_ROW after every row
+__device__ static inline bool topn_row_less(const TopnKeys& K, uint32_t a, uint32_t b) {
+    if (a == b) return false;
+    if (b == TOPN_PAD_ROW) return true;
+    if (a == TOPN_PAD_ROW) return false;
+    for (int k = 0; k < K.n_keys; k++) {
+        uint32_t ca, cb;
+        uint64_t va, vb;
+        topn_load(K.col[k], K.nulls[k], K.type[k], K.flags[k], a, ca, va);
+        topn_load(K.col[k], K.nulls[k], K.type[k], K.flags[k], b, cb, vb);
+        if (ca != cb) return ca < cb;
+        if (va != vb) return va < vb;
+    }
+    return a < b;
+}
+
+__device__ static inline bool topn_less(const TopnKeys& K, uint64_t k0a, uint32_t a,
+                                        uint64_t k0b, uint32_t b) {
+    if (k0a != k0b) return k0a < k0b;
+    return topn_row_less(K, a, b);
+}
+
+// class pass: per-thread register counts (a 3-bin LDS histogram would
+// serialize on the non-NULL bin), block reduce, one atomic set per block
+__global__ void __launch_bounds__(BLOCK)
+k_topn_class(const void* __restrict__ col, const uint8_t* __restrict__ nulls, int type,
+             int flags, const uint32_t* __restrict__ cand, uint64_t n_cand, uint64_t chunk,
+             TopnState* __restrict__ st, uint32_t* __restrict__ blockhist) {
+    uint64_t p0 = (uint64_t)blockIdx.x * chunk;
+    uint64_t p1 = p0 + chunk < n_cand ? p0 + chunk : n_cand;
+    uint32_t c0 = 0, c2 = 0;
+    uint64_t nmn = 0, mx = 0;
+    for (uint64_t tb = p0; tb < p1; tb += TOPN_TILE) {
+        uint32_t row[TOPN_ITEMS], cls[TOPN_ITEMS];
+        uint64_t v[TOPN_ITEMS];
+        topn_tile_load(col, nulls, type, flags, cand, tb, p1, row, cls, v);
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++) {
+            c0 += cls[j] == 0u;
+            c2 += cls[j] == 2u;
+            if (cls[j] == 1u) {
+                nmn = ~v[j] > nmn ? ~v[j] : nmn;
+                mx = v[j] > mx ? v[j] : mx;
+            }
+        }
+    }
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        c0 += __shfl_down(c0, o);
+        c2 += __shfl_down(c2, o);
+        uint64_t a = __shfl_down(nmn, o), b = __shfl_down(mx, o);
+        nmn = a > nmn ? a : nmn;
+        mx = b > mx ? b : mx;
+    }
+    __shared__ uint32_t s_c0[BLOCK / WAVE], s_c2[BLOCK / WAVE];
+    __shared__ uint64_t s_mn[BLOCK / WAVE], s_mx[BLOCK / WAVE];
+    int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    if (lane == 0) {
+        s_c0[wave] = c0;
+        s_c2[wave] = c2;
+        s_mn[wave] = nmn;
+        s_mx[wave] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < BLOCK / WAVE; w++) {
+            c0 += s_c0[w];
+            c2 += s_c2[w];
+            nmn = s_mn[w] > nmn ? s_mn[w] : nmn;
+            mx = s_mx[w] > mx ? s_mx[w] : mx;
+        }
+        uint32_t tot = p1 > p0 ? (uint32_t)(p1 - p0) : 0u;
+        uint32_t c1 = tot - c0 - c2;
+        uint32_t* bh = blockhist + (uint64_t)blockIdx.x * TOPN_NB;
+        bh[0] = c0;
+        bh[1] = c1;
+        bh[2] = c2;
+        if (c0) atomicAdd(&st->hist[0], c0);
+        if (c1) atomicAdd(&st->hist[1], c1);
+        if (c2) atomicAdd(&st->hist[2], c2);
+        if (c1) {
+            atomicMax(&st->nvmin, (unsigned long long)nmn);
+            atomicMax(&st->vmax, (unsigned long long)mx);
+        }
+    }
+}
+
+// digit pass: candidates are all non-NULL here (the class pass ran first)
+__global__ void __launch_bounds__(BLOCK)
+k_topn_hist(const void* __restrict__ col, int type, int flags,
+            const uint32_t* __restrict__ cand, uint64_t n_cand, uint64_t chunk, int shift,
+            TopnState* __restrict__ st, uint32_t* __restrict__ blockhist) {
+    __shared__ uint32_t s_hist[TOPN_NB];
+    for (uint32_t i = threadIdx.x; i < TOPN_NB; i += BLOCK) s_hist[i] = 0;
+    __syncthreads();
+    uint64_t p0 = (uint64_t)blockIdx.x * chunk;
+    uint64_t p1 = p0 + chunk < n_cand ? p0 + chunk : n_cand;
+    for (uint64_t tb = p0; tb < p1; tb += TOPN_TILE) {
+        uint32_t row[TOPN_ITEMS], cls[TOPN_ITEMS];
+        uint64_t v[TOPN_ITEMS];
+        topn_tile_load(col, nullptr, type, flags, cand, tb, p1, row, cls, v);
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++) {
+            bool valid = cls[j] != TOPN_CLS_NONE;
+            uint32_t bin = (uint32_t)(v[j] >> shift) & (TOPN_NB - 1);
+            // valid lanes are a prefix of the wave, so lane 0 is valid
+            // whenever any lane is; a wave whose rows share one digit (sorted
+            // input, low-cardinality keys, all-equal rows) adds once instead
+            // of serializing 64 LDS atomics on one address
+            uint32_t b0 = __shfl(bin, 0);
+            if (__all(!valid || bin == b0)) {
+                unsigned long long vm = __ballot(valid);
+                if ((threadIdx.x & (WAVE - 1)) == 0 && vm)
+                    atomicAdd(&s_hist[b0], (uint32_t)__popcll(vm));
+            } else if (valid) {
+                atomicAdd(&s_hist[bin], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* bh = blockhist + (uint64_t)blockIdx.x * TOPN_NB;
+    for (uint32_t i = threadIdx.x; i < TOPN_NB; i += BLOCK) {
+        uint32_t h = s_hist[i];
+        bh[i] = h;
+        if (h) atomicAdd(&st->hist[i], h);
+    }
+}
+
+// inclusive block scan over BLOCK u64 partials (Hillis-Steele in LDS)
+__device__ static inline unsigned long long topn_block_scan(unsigned long long x,
+                                                            unsigned long long* s) {
+    s[threadIdx.x] = x;
+    __syncthreads();
+    for (int o = 1; o < BLOCK; o <<= 1) {
+        unsigned long long y = threadIdx.x >= (unsigned)o ? s[threadIdx.x - o] : 0ull;
+        __syncthreads();
+        s[threadIdx.x] += y;
+        __syncthreads();
+    }
+    return s[threadIdx.x];
+}
+
+// plan (one block): pivot bin p = the bin holding the R-th candidate in key
+// order; r_before = candidates strictly before it; blk_off = exclusive scan
+// of the per-block pivot counts; re-arms the accumulators for the next pass
+__global__ void __launch_bounds__(BLOCK)
+k_topn_plan(TopnState* __restrict__ st, const uint32_t* __restrict__ blockhist, uint32_t nb,
+            uint32_t nbins, unsigned long long R) {
+    constexpr int PER = TOPN_NB / BLOCK;
+    __shared__ unsigned long long s_scan[BLOCK];
+    __shared__ uint32_t s_p;
+    if (threadIdx.x == 0) s_p = 0xFFFFFFFFu;
+    uint32_t h[PER];
+    unsigned long long loc = 0;
+    for (int j = 0; j < PER; j++) {
+        uint32_t i = threadIdx.x * PER + j;
+        h[j] = i < nbins ? st->hist[i] : 0u;
+        st->hist[i] = 0u;
+        loc += h[j];
+    }
+    unsigned long long ex = topn_block_scan(loc, s_scan) - loc;
+    for (int j = 0; j < PER; j++) {
+        if (h[j] && ex < R && R <= ex + h[j]) {
+            s_p = threadIdx.x * PER + j;
+            st->r_pivot = threadIdx.x * PER + j;
+            st->r_before = (uint32_t)ex;
+            st->r_npivot = h[j];
+        }
+        ex += h[j];
+    }
+    __syncthreads();
+    uint32_t p = s_p;
+    if (p == 0xFFFFFFFFu) { // R outside [1, candidates]: host turns this into an error
+        if (threadIdx.x == 0) st->r_pivot = 0xFFFFFFFFu;
+        return;
+    }
+    constexpr int BPER = TOPN_MAX_BLOCKS / BLOCK;
+    uint32_t c[BPER];
+    unsigned long long bl = 0;
+    for (int j = 0; j < BPER; j++) {
+        uint32_t b = threadIdx.x * BPER + j;
+        c[j] = b < nb ? blockhist[(uint64_t)b * TOPN_NB + p] : 0u;
+        bl += c[j];
+    }
+    unsigned long long bex = topn_block_scan(bl, s_scan) - bl;
+    for (int j = 0; j < BPER; j++) {
+        st->blk_off[threadIdx.x * BPER + j] = (uint32_t)bex;
+        bex += c[j];
+    }
+    if (threadIdx.x == 0) {
+        st->r_vmin = ~st->nvmin;
+        st->r_vmax = st->vmax;
+        st->nvmin = 0ull;
+        st->vmax = 0ull;
+    }
+}
+
+// compact: same block->row-range mapping as the histogram pass. Tile rows are
+// striped (item j of thread t = tile_base + j*BLOCK + t) so loads coalesce;
+// output order = (item, wave, lane) = ascending candidate position.
+__global__ void __launch_bounds__(BLOCK)
+k_topn_compact(const void* __restrict__ col, const uint8_t* __restrict__ nulls, int type,
+               int flags, int mode, int shift, const uint32_t* __restrict__ cand,
+               uint64_t n_cand, uint64_t chunk, TopnState* __restrict__ st,
+               uint32_t* __restrict__ winners, uint64_t win_cap,
+               uint32_t* __restrict__ cand_out, uint64_t out_cap) {
+    constexpr int NW = BLOCK / WAVE;
+    __shared__ uint32_t s_cnt[TOPN_ITEMS][NW];
+    const uint32_t p = st->r_pivot;
+    uint64_t run = st->blk_off[blockIdx.x];
+    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    uint64_t p0 = (uint64_t)blockIdx.x * chunk;
+    uint64_t p1 = p0 + chunk < n_cand ? p0 + chunk : n_cand;
+    for (uint64_t tb = p0; tb < p1; tb += TOPN_TILE) {
+        uint32_t row[TOPN_ITEMS], cls[TOPN_ITEMS], pre[TOPN_ITEMS];
+        uint64_t v[TOPN_ITEMS];
+        bool isp[TOPN_ITEMS], isw[TOPN_ITEMS];
+        topn_tile_load(col, mode == 0 ? nulls : nullptr, type, flags, cand, tb, p1, row, cls,
+                       v);
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++) {
+            bool valid = cls[j] != TOPN_CLS_NONE;
+            uint32_t bin = mode == 0 ? cls[j] : (uint32_t)(v[j] >> shift) & (TOPN_NB - 1);
+            isp[j] = valid && bin == p;
+            isw[j] = valid && bin < p;
+        }
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++) {
+            unsigned long long bal = __ballot(isp[j]);
+            pre[j] = (uint32_t)__popcll(bal & lt);
+            if (lane == 0) s_cnt[j][wave] = (uint32_t)__popcll(bal);
+        }
+        __syncthreads();
+        uint32_t acc = 0, mybase[TOPN_ITEMS] = {};
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++)
+#pragma unroll
+            for (int w = 0; w < NW; w++) {
+                if (w == wave) mybase[j] = acc;
+                acc += s_cnt[j][w];
+            }
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++) {
+            uint64_t o = run + mybase[j] + pre[j];
+            if (isp[j] && o < out_cap) cand_out[o] = row[j];
+        }
+        run += acc;
+#pragma unroll
+        for (int j = 0; j < TOPN_ITEMS; j++) {
+            unsigned long long bal = __ballot(isw[j]);
+            if (bal) { // wave-uniform
+                int leader = __ffsll((long long)bal) - 1;
+                uint32_t wb = 0;
+                if (lane == leader) wb = atomicAdd(&st->win_cursor, (uint32_t)__popcll(bal));
+                wb = __shfl(wb, leader);
+                uint64_t o = (uint64_t)wb + (uint32_t)__popcll(bal & lt);
+                if (isw[j] && o < win_cap) winners[o] = row[j];
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// survivors = winners ++ first `take` candidates, padded to total (pow2)
+// with TOPN_PAD_ROW; k0 = (class << 62) | v (int32: exact; 64-bit: v >> 2).
+// Real classes are 0..2, so the pad's k0 = ~0 sorts after every row.
+__global__ void k_topn_fill(TopnKeys K, uint32_t* __restrict__ idx,
+                            uint64_t* __restrict__ k0, uint64_t n_win,
+                            const uint32_t* __restrict__ cand, uint64_t take,
+                            uint64_t total) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+         i += stride) {
+        uint32_t row;
+        if (i < n_win) row = idx[i];
+        else if (i < n_win + take) row = cand ? cand[i - n_win] : (uint32_t)(i - n_win);
+        else row = TOPN_PAD_ROW;
+        uint64_t kk = ~0ull;
+        if (row != TOPN_PAD_ROW) {
+            uint32_t cls;
+            uint64_t v;
+            topn_load(K.col[0], K.nulls[0], K.type[0], K.flags[0], row, cls, v);
+            kk = ((uint64_t)cls << 62) | (K.type[0] == 0 ? v : (v >> 2));
+        }
+        idx[i] = row;
+        k0[i] = kk;
+    }
+}
+
+// bitonic strides inside one LDS tile: for k in [k_first, k_last], strides
+// j = min(k/2, tile/2) .. 1. Direction comes from the GLOBAL element index.
+__global__ void __launch_bounds__(TOPN_SORT_TPB)
+k_topn_sort_lds(TopnKeys K, uint32_t* __restrict__ idx, uint64_t* __restrict__ k0,
+                uint64_t total, uint64_t k_first, uint64_t k_last) {
+    __shared__ uint64_t s_k0[TOPN_SORT_TILE];
+    __shared__ uint32_t s_idx[TOPN_SORT_TILE];
+    uint32_t tn = total < TOPN_SORT_TILE ? (uint32_t)total : TOPN_SORT_TILE;
+    uint64_t gb = (uint64_t)blockIdx.x * TOPN_SORT_TILE;
+    for (uint32_t i = threadIdx.x; i < tn; i += TOPN_SORT_TPB) {
+        s_k0[i] = k0[gb + i];
+        s_idx[i] = idx[gb + i];
+    }
+    __syncthreads();
+    for (uint64_t k = k_first; k <= k_last; k <<= 1) {
+        uint32_t j0 = (k >> 1) < (uint64_t)(tn >> 1) ? (uint32_t)(k >> 1) : (tn >> 1);
+        for (uint32_t j = j0; j > 0; j >>= 1) {
+            for (uint32_t t = threadIdx.x; t < (tn >> 1); t += TOPN_SORT_TPB) {
+                uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                uint32_t ij = i | j;
+                bool up = ((gb + i) & k) == 0;
+                uint64_t ka = s_k0[i], kb = s_k0[ij];
+                uint32_t ra = s_idx[i], rb = s_idx[ij];
+                bool sw = up ? topn_less(K, kb, rb, ka, ra) : topn_less(K, ka, ra, kb, rb);
+                if (sw) {
+                    s_k0[i] = kb;
+                    s_k0[ij] = ka;
+                    s_idx[i] = rb;
+                    s_idx[ij] = ra;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = threadIdx.x; i < tn; i += TOPN_SORT_TPB) {
+        k0[gb + i] = s_k0[i];
+        idx[gb + i] = s_idx[i];
+    }
+}
+
+// one bitonic stride j >= tile over global memory
+__global__ void k_topn_sort_global(TopnKeys K, uint32_t* __restrict__ idx,
+                                   uint64_t* __restrict__ k0, uint64_t total, uint64_t k,
+                                   uint64_t j) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < (total >> 1);
+         t += stride) {
+        uint64_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        uint64_t ij = i | j;
+        bool up = (i & k) == 0;
+        uint64_t ka = k0[i], kb = k0[ij];
+        uint32_t ra = idx[i], rb = idx[ij];
+        bool sw = up ? topn_less(K, kb, rb, ka, ra) : topn_less(K, ka, ra, kb, rb);
+        if (sw) {
+            k0[i] = kb;
+            k0[ij] = ka;
+            idx[i] = rb;
+            idx[ij] = ra;
+        }
+    }
+}
+
+namespace {
+struct TopnWork { // frees the call's scratch on every return path
+    void* p[3] = {nullptr, nullptr, nullptr};
+    ~TopnWork() {
+        for (void* q : p)
+            if (q) (void)hipFree(q);
+    }
+};
+} // namespace
+
+int gpue_topn(gpue_session* s, gpue_dbuf** key_cols, gpue_dbuf** key_nulls,
+              const int32_t* key_type, const int32_t* key_flags, int n_keys, uint64_t n_rows,
+              uint64_t offset, uint64_t limit, gpue_dbuf* out_row_idx, uint64_t* out_count) {
+    ARG_CHECK(s && key_cols && key_type && key_flags && out_count);
+    ARG_CHECK(n_keys >= 1 && n_keys <= TOPN_MAX_KEYS);
+    ARG_CHECK(n_rows < (1ull << 32));
+    TopnKeys K;
+    memset(&K, 0, sizeof(K));
+    K.n_keys = n_keys;
+    for (int k = 0; k < n_keys; k++) {
+        ARG_CHECK(key_type[k] >= 0 && key_type[k] <= 2);
+        ARG_CHECK(key_cols[k] != nullptr);
+        ARG_CHECK(key_cols[k]->bytes >= n_rows * (key_type[k] == 0 ? 4u : 8u));
+        gpue_dbuf* nm = key_nulls ? key_nulls[k] : nullptr;
+        ARG_CHECK(!nm || nm->bytes >= n_rows);
+        K.col[k] = key_cols[k]->ptr;
+        K.nulls[k] = nm ? (const uint8_t*)nm->ptr : nullptr;
+        K.type[k] = key_type[k];
+        K.flags[k] = key_flags[k] & 3;
+    }
+    const uint64_t n = n_rows;
+    const uint64_t count = offset >= n ? 0 : (limit < n - offset ? limit : n - offset);
+    ARG_CHECK(count == 0 || (out_row_idx && out_row_idx->bytes >= count * 4));
+    *out_count = count;
+    if (count == 0) return GPUE_OK;
+    const uint64_t Kq = offset + count; // rows needed from the head of the order
+
+    const bool direct = Kq >= n || n <= TOPN_SORT_TILE;
+    const uint64_t s_max = direct ? n : (Kq > TOPN_SORT_TILE ? Kq : TOPN_SORT_TILE);
+    uint64_t pad_max = 1;
+    while (pad_max < s_max) pad_max <<= 1;
+
+    TopnWork w;
+    // p[0]: survivors (k0 u64[pad] then row u32[pad]); p[1]: state + per-block
+    // histograms; p[2]: the two candidate ping-pong lists (sized on first use)
+    HIP_CHECK(hipMalloc(&w.p[0], pad_max * 12));
+    uint64_t* d_k0 = (uint64_t*)w.p[0];
+    uint32_t* d_surv = (uint32_t*)(d_k0 + pad_max);
+    const uint32_t* cand = nullptr; // nullptr = identity (every row, in order)
+    uint64_t n_cand = n, n_win = 0, take = n;
+
+    if (!direct) {
+        const uint64_t st_bytes = (sizeof(TopnState) + 255) & ~255ull;
+        HIP_CHECK(hipMalloc(&w.p[1], st_bytes + (uint64_t)TOPN_MAX_BLOCKS * TOPN_NB * 4));
+        TopnState* st = (TopnState*)w.p[1];
+        uint32_t* blockhist = (uint32_t*)((char*)w.p[1] + st_bytes);
+        HIP_CHECK(hipMemsetAsync(st, 0, sizeof(TopnState), s->stream));
+        uint32_t* cbuf[2] = {nullptr, nullptr};
+        int cur = 0;
+        uint64_t R = Kq;
+        bool done = false;
+        uint64_t vmin = 0, vmax = 0;
+        uint32_t pivot = 0;
+
+        // one select pass over key k: mode 0 = class (3 bins), 1 = digit
+        auto pass = [&](int mode, int k, int shift) -> int {
+            uint64_t tiles = (n_cand + TOPN_TILE - 1) / TOPN_TILE;
+            uint32_t nb = (uint32_t)(tiles < TOPN_MAX_BLOCKS ? tiles : TOPN_MAX_BLOCKS);
+            uint64_t chunk = (tiles + nb - 1) / nb * TOPN_TILE;
+            if (mode == 0)
+                hipLaunchKernelGGL(k_topn_class, dim3(nb), dim3(BLOCK), 0, s->stream, K.col[k],
+                                   K.nulls[k], K.type[k], K.flags[k], cand, n_cand, chunk, st,
+                                   blockhist);
+            else
+                hipLaunchKernelGGL(k_topn_hist, dim3(nb), dim3(BLOCK), 0, s->stream, K.col[k],
+                                   K.type[k], K.flags[k], cand, n_cand, chunk, shift, st,
+                                   blockhist);
+            hipLaunchKernelGGL(k_topn_plan, dim3(1), dim3(BLOCK), 0, s->stream, st,
+                               (const uint32_t*)blockhist, nb, mode == 0 ? 3u : TOPN_NB,
+                               (unsigned long long)R);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(s->pinned, &st->r_vmin, 32, hipMemcpyDeviceToHost,
+                                     s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            uint64_t r64[2];
+            uint32_t r32[4];
+            memcpy(r64, s->pinned, 16);
+            memcpy(r32, (char*)s->pinned + 16, 16);
+            vmin = r64[0];
+            vmax = r64[1];
+            pivot = r32[0];
+            uint64_t before = r32[1], npivot = r32[2];
+            if (pivot == 0xFFFFFFFFu || before >= R || npivot > n_cand ||
+                before + npivot < R) {
+                snprintf(g_err, sizeof(g_err), "gpue_topn: inconsistent select pass");
+                return GPUE_ERR_HIP;
+            }
+            if (npivot < n_cand) {
+                if (!cbuf[0]) {
+                    HIP_CHECK(hipMalloc(&w.p[2], npivot * 8));
+                    cbuf[0] = (uint32_t*)w.p[2];
+                    cbuf[1] = cbuf[0] + npivot;
+                }
+                uint32_t* out = cbuf[cur];
+                hipLaunchKernelGGL(k_topn_compact, dim3(nb), dim3(BLOCK), 0, s->stream,
+                                   K.col[k], K.nulls[k], K.type[k], K.flags[k], mode, shift,
+                                   cand, n_cand, chunk, st, d_surv, pad_max, out, npivot);
+                HIP_CHECK(hipGetLastError());
+                cand = out;
+                cur ^= 1;
+            }
+            n_win += before;
+            R -= before;
+            n_cand = npivot;
+            if (R == n_cand || n_win + n_cand <= TOPN_SORT_TILE) {
+                take = n_cand;
+                done = true;
+            }
+            return GPUE_OK;
+        };
+
+        for (int k = 0; k < n_keys && !done; k++) {
+            int rc = pass(0, k, 0);
+            if (rc != GPUE_OK) return rc;
+            // pivot on a NULL class, or one distinct value left: this key ties
+            if (done || pivot != 1u || vmin == vmax) continue;
+            int hb = 63 - __builtin_clzll(vmin ^ vmax); // first varying bit
+            int shift = hb + 1 > TOPN_RBITS ? hb + 1 - TOPN_RBITS : 0;
+            for (;;) {
+                rc = pass(1, k, shift);
+                if (rc != GPUE_OK) return rc;
+                if (done || shift == 0) break;
+                shift = shift > TOPN_RBITS ? shift - TOPN_RBITS : 0;
+            }
+        }
+        // keys ran out: the candidates tie on every key and are in ascending
+        // row order, so the first R of them are the stable answer
+        if (!done) take = R;
+    }
+
+    const uint64_t S = n_win + take;
+    uint64_t total = 1;
+    while (total < S) total <<= 1;
+    hipLaunchKernelGGL(k_topn_fill, dim3(grid_for(total)), dim3(BLOCK), 0, s->stream, K, d_surv,
+                       d_k0, n_win, cand, take, total);
+    if (total >= 2) {
+        const uint64_t tile = TOPN_SORT_TILE;
+        uint32_t nblk = (uint32_t)(total > tile ? total / tile : 1);
+        hipLaunchKernelGGL(k_topn_sort_lds, dim3(nblk), dim3(TOPN_SORT_TPB), 0, s->stream, K,
+                           d_surv, d_k0, total, (uint64_t)2, total < tile ? total : tile);
+        for (uint64_t k = tile * 2; k <= total; k <<= 1) {
+            for (uint64_t j = k >> 1; j >= tile; j >>= 1)
+                hipLaunchKernelGGL(k_topn_sort_global, dim3(grid_for(total >> 1)), dim3(BLOCK),
+                                   0, s->stream, K, d_surv, d_k0, total, k, j);
+            hipLaunchKernelGGL(k_topn_sort_lds, dim3(nblk), dim3(TOPN_SORT_TPB), 0, s->stream,
+                               K, d_surv, d_k0, total, k, k);
+        }
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out_row_idx->ptr, d_surv + offset, count * 4,
+                             hipMemcpyDeviceToDevice, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GPUE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // PlainPage numeric decode (plain_page.h:51,83-102,148-158): u32 LE count
 // header + raw LE values — the fallback encoding every numeric type can
 // take (encoding_info.cpp). Decode is a validated device copy.

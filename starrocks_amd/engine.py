@@ -193,6 +193,8 @@ def _declare(lib):
         "gpue_sbf_build_i32": (c_i32, [c_vp, c_vp, c_u64, c_i32, c_vp]),
         "gpue_sbf_test_i32": (c_i32, [c_vp, c_vp, c_u64, c_vp, c_i32, c_vp]),
         "gpue_topk_i64": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_i32, c_vp, c_vp]),
+        "gpue_topn": (c_i32, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp,
+                              c_i32, c_u64, c_u64, c_u64, c_vp, ctypes.POINTER(c_u64)]),
         "gpue_page_decode_rle_i32": (c_i32, [c_vp, c_vp, c_u64, c_vp]),
         "gpue_page_decode_plain_i32": (c_i32, [c_vp, c_vp, c_u64, c_vp]),
         "gpue_page_decode_rle_bool": (c_i32, [c_vp, c_vp, c_u64, c_vp]),
@@ -1034,6 +1036,48 @@ class Engine:
                                                ok.ctypes.data_as(c_vp),
                                                ov.ctypes.data_as(c_vp)))
         return ok, ov
+
+    # --- general TopN (chunks_sorter_topn.cpp under SortDesc semantics) ---
+    TOPN_I32, TOPN_I64, TOPN_U64 = 0, 1, 2
+
+    def topn_into(self, keys, n_rows, limit, offset, out: DBuf) -> int:
+        """gpue_topn into a caller-owned u32 index buffer (out may be None
+        when the count is 0); returns the count. keys: list of
+        (DBuf, nulls_or_None, type, desc, nulls_first), most significant
+        first; type 0 int32 / 1 int64 / 2 uint64; nulls is a u8 mask DBuf
+        (nonzero = NULL row)."""
+        nk = len(keys)
+        cols = (c_vp * max(nk, 1))(*[k[0]._h for k in keys])
+        nulls = (c_vp * max(nk, 1))(*[k[1]._h if k[1] is not None else None for k in keys])
+        types = np.array([k[2] for k in keys], np.int32)
+        flags = np.array([(1 if k[3] else 0) | (2 if k[4] else 0) for k in keys], np.int32)
+        cnt = c_u64()
+        _ck(self._lib, self._lib.gpue_topn(
+            self._h, cols, nulls, types.ctypes.data_as(c_vp), flags.ctypes.data_as(c_vp),
+            nk, n_rows, offset, limit, out._h if out is not None else None,
+            ctypes.byref(cnt)))
+        return cnt.value
+
+    def topn(self, keys, n_rows, limit, offset=0):
+        """Multi-key ORDER BY ... LIMIT/OFFSET: returns (idx, count) — idx a
+        device buffer of u32 row indices in result order (rows equal on every
+        key in ascending row index), count = min(limit, max(n_rows - offset,
+        0)). Materialize payload columns with gather_u32/gather_u64."""
+        count = min(limit, max(n_rows - offset, 0))
+        out = self.alloc(max(count, 1) * 4)
+        try:
+            got = self.topn_into(keys, n_rows, limit, offset, out)
+        except BaseException:
+            out.free()
+            raise
+        return out, got
+
+    def topn_indices(self, keys, n_rows, limit, offset=0) -> np.ndarray:
+        """topn() with the row indices copied to the host."""
+        out, cnt = self.topn(keys, n_rows, limit, offset)
+        idx = out.d2h(np.uint32, cnt)
+        out.free()
+        return idx
 
     # ---- stream event timing (bench) ----
     def timer_start(self):

@@ -429,6 +429,120 @@ class FinalAggSink(Operator):
         return keys[order], sums[order], cnts[order]
 
 
+class TopNSinkOperator(Operator):
+    """ORDER BY ... LIMIT/OFFSET sink — the ChunksSorterTopn analog
+    (exec/chunks_sorter_topn.cpp: update() per pushed chunk keeps a bounded
+    candidate set, done()/get_next yields the ordered rows).
+
+    Chunks are {"n": rows, "cols": [DBuf, ...]}; col_dtypes gives each
+    column's numpy dtype (4- or 8-byte items). sort_keys is a list of
+    (col_index, type, desc), most significant first, type as Engine.topn
+    (0 int32 / 1 int64 / 2 uint64). Sort keys are NOT NULL columns here: the
+    candidate set is re-materialized with gather_u32/gather_u64, and there is
+    no u8 gather for a null mask — nullable keys go through Engine.topn
+    directly.
+
+    Per push: topn over the chunk for K = offset+limit rows, gather every
+    column through the surviving indices, append to the candidate columns;
+    when the append would pass the bound (bound_factor * K rows, >= 2K) the
+    candidates are first cut back to K by topn over themselves. result() runs
+    the final topn with the real offset/limit.
+
+    Stable tie-break across chunks: topn returns rows that are equal on every
+    key in ascending row index, the candidate set is kept in that sorted
+    order, and new survivors are appended behind it in arrival order. So rows
+    equal on every key always sit in the candidate set in global row order,
+    a later topn over the candidates (whose tie-break is candidate position)
+    preserves it, and whenever ties are cut the latest-arrived rows go first
+    — exactly the one-shot result, for free.
+
+    Uses only engine.alloc / topn / gather_u32 / gather_u64 / dbuf_d2d and
+    DBuf.d2h / free, so the merge logic runs against a numpy stand-in engine
+    without a GPU."""
+
+    def __init__(self, engine, sort_keys, col_dtypes, limit, offset=0, bound_factor=4):
+        super().__init__()
+        assert bound_factor >= 2 and limit >= 0 and offset >= 0
+        self._e = engine
+        self._keys = list(sort_keys)
+        self._dtypes = [np.dtype(d) for d in col_dtypes]
+        assert all(d.itemsize in (4, 8) for d in self._dtypes)
+        self._limit = limit
+        self._offset = offset
+        self._k = offset + limit
+        self.capacity = bound_factor * self._k   # the stated candidate bound (rows)
+        self.max_candidate_rows = 0              # high-water mark, for tests
+        self._cand = None                        # candidate columns, capacity rows each
+        self._n = 0
+
+    def need_input(self):
+        return not self._finishing
+
+    def has_output(self):
+        return False
+
+    def _key_desc(self, cols):
+        return [(cols[c], None, t, d, False) for c, t, d in self._keys]
+
+    def _gather(self, cols, idx, cnt):
+        out = []
+        for col, dt in zip(cols, self._dtypes):
+            g = self._e.alloc(max(cnt, 1) * dt.itemsize)
+            if cnt:
+                (self._e.gather_u32 if dt.itemsize == 4 else self._e.gather_u64)(
+                    col, idx, cnt, g)
+            out.append(g)
+        return out
+
+    def _append(self, cols, cnt):
+        if self._cand is None:
+            self._cand = [self._e.alloc(max(self.capacity, 1) * dt.itemsize)
+                          for dt in self._dtypes]
+        for src, dst, dt in zip(cols, self._cand, self._dtypes):
+            self._e.dbuf_d2d(src, dst, cnt * dt.itemsize, 0, self._n * dt.itemsize)
+        self._n += cnt
+        self.max_candidate_rows = max(self.max_candidate_rows, self._n)
+
+    def _cut(self):
+        """Candidates -> their own top K, sorted."""
+        idx, cnt = self._e.topn(self._key_desc(self._cand), self._n, self._k, 0)
+        kept = self._gather(self._cand, idx, cnt)
+        idx.free()
+        self._n = 0
+        self._append(kept, cnt)
+        for b in kept:
+            b.free()
+
+    def push_chunk(self, chunk):
+        n, cols = chunk["n"], chunk["cols"]
+        if n and self._k:
+            idx, cnt = self._e.topn(self._key_desc(cols), n, self._k, 0)
+            surv = self._gather(cols, idx, cnt)
+            idx.free()
+            if self._n + cnt > self.capacity:
+                self._cut()          # -> at most K rows; K + cnt <= 2K <= capacity
+            self._append(surv, cnt)
+            for b in surv:
+                b.free()
+        for b in cols:
+            b.free()
+
+    def result(self):
+        """Final ordered rows as one numpy array per column."""
+        if self._cand is None:
+            return [np.empty(0, dt) for dt in self._dtypes]
+        idx, cnt = self._e.topn(self._key_desc(self._cand), self._n, self._limit,
+                                self._offset)
+        final = self._gather(self._cand, idx, cnt)
+        idx.free()
+        out = [b.d2h(dt, cnt) for b, dt in zip(final, self._dtypes)]
+        for b in final + self._cand:
+            b.free()
+        self._cand = None
+        self._n = 0
+        return out
+
+
 def q1_operator_pipeline(engine, seed, total_rows, year=1993,
                          chunk_rows=DEFAULT_CHUNK_ROWS, dim_chunk_rows=1000):
     """Config-2's plan as the reference would run it — dim source -> build
