@@ -4718,6 +4718,233 @@ k_q21_star_agg_pfq3(const int32_t* __restrict__ pk, const int32_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// Staged-cascade deferred-load q21 (GPUE_Q21_PF=8): pfq3's bytes, fetched
+// with more of them in flight. pfq3 issues the next pk pair only after a
+// drain's whole dependent chain (pfirst -> sk -> sbits -> od -> dfirst -> rv)
+// has returned, and runs that chain in one wave with ~50 % and then ~10 % of
+// the lanes alive. Here
+//  PREFETCH: the pk pair of iteration t+1 is loaded before any push or drain
+//            of iteration t (register double buffer, NT loads);
+//  B >= 1:   the confirm chain is cut into three per-wave LDS queues, each
+//            drained a full 64-lane batch at a time until the final flush:
+//              Q1 {pk,row}    -> gather pfirst          -> brand != 0 to Q2
+//              Q2 {row,brand} -> gather sk, test sbits  -> survivors to Q3
+//              Q3 {row,brand} -> od + rv together, dfirst, LDS atomic
+//            Q3 drains at >= 64*B entries, B per lane, all B gathers of a
+//            step issued before any is consumed (the longest chain);
+//  B == 0:   pfq3's single queue and inline confirm (the prefetch-only A/B).
+// A stage is drained right after the push that can fill it, so fills stay
+// Q1 <= 127, Q2 <= 127, Q3 <= 64*B+63. Q2 and Q3 hold the same {row,brand}
+// entries and share one array, Q2 growing up from slot 0 and Q3 down from
+// slot QS-1: Q2 is above 63 only between Q1's push and Q2's own drain, when
+// Q3 <= 64*B-1, and Q3 is above 64*B-1 only between Q2's push (Q2 <= 63 by
+// then) and its own drain, so Q2 + Q3 <= 126 + 64*B = QS and the two never
+// meet. LDS: 2x32 KB folds + 56,000 B groups + 16 KB Q1 + 16*QS*6 B =
+// 156,160 B (B=1) / 162,304 B (B=2), static, 1 block/CU.
+// All fills come from ballots, so they and every loop condition are
+// wave-uniform, as in pfq.
+// ---------------------------------------------------------------------------
+template <bool PREFETCH, int B>
+__global__ __launch_bounds__(BLOCK_Q21) void
+k_q21_star_agg_pfq4(const int32_t* __restrict__ pk, const int32_t* __restrict__ sk,
+                    const int32_t* __restrict__ od, const int32_t* __restrict__ rv,
+                    uint64_t n, const uint32_t* __restrict__ prefilter, int64_t psmin,
+                    uint64_t psint, const uint16_t* __restrict__ pfirst,
+                    const uint32_t* __restrict__ sbits, int64_t ssmin, uint64_t ssint,
+                    const uint16_t* __restrict__ dfirst, int64_t dmin,
+                    unsigned long long* __restrict__ group_sums) {
+    constexpr int B3 = B > 0 ? B : 1;
+    constexpr int QS = B > 0 ? 126 + 64 * B3 : 1;
+    __shared__ uint32_t pfa[1 << 13];
+    __shared__ uint32_t pfb[1 << 13];
+    __shared__ unsigned long long g[NG_Q21];
+    __shared__ int2 q1[BLOCK_Q21 / WAVE][128];     // {pk, row32}
+    __shared__ uint32_t qrow[BLOCK_Q21 / WAVE][QS]; // Q2 up from 0, Q3 down from QS-1
+    __shared__ uint16_t qbr[BLOCK_Q21 / WAVE][QS];
+    for (uint32_t w = threadIdx.x; w < (1u << 13); w += blockDim.x) {
+        pfa[w] = prefilter[w];
+        pfb[w] = prefilter[(1u << 13) + w];
+    }
+    for (int j = threadIdx.x; j < NG_Q21; j += blockDim.x) g[j] = 0;
+    __syncthreads();
+    const int wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t n1 = 0, n2 = 0, n3 = 0; // wave-uniform fills (ballot counts)
+    const uint64_t n4 = n / 4;
+    const int4* __restrict__ pk4 = (const int4*)pk;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    // Q3: B3 entries per lane from the top of the queue; cnt = 64*B3 for a
+    // full batch, the fill at the final flush
+    auto drain3 = [&](uint32_t cnt) {
+        uint32_t r[B3], b[B3], y[B3];
+        int32_t o[B3], v[B3];
+        bool act[B3];
+        #pragma unroll
+        for (int k = 0; k < B3; k++) {
+            act[k] = k * 64 + lane < cnt;
+            uint32_t slot = QS - 1 - (n3 - cnt + k * 64 + lane);
+            r[k] = act[k] ? qrow[wid][slot] : 0u;
+            b[k] = act[k] ? qbr[wid][slot] : 0u;
+        }
+        n3 -= cnt;
+        #pragma unroll
+        for (int k = 0; k < B3; k++)
+            if (act[k]) {
+                o[k] = od[r[k]];
+                v[k] = rv[r[k]];
+            }
+        #pragma unroll
+        for (int k = 0; k < B3; k++)
+            if (act[k]) y[k] = dfirst[o[k] - dmin];
+        #pragma unroll
+        for (int k = 0; k < B3; k++)
+            if (act[k])
+                atomicAdd(&g[(y[k] - 1) * 1000 + (b[k] - 1)],
+                          (unsigned long long)(int64_t)v[k]);
+    };
+    // Q2: the top cnt entries (64, or the fill at the final flush)
+    auto drain2 = [&](uint32_t cnt) {
+        bool act = lane < cnt;
+        uint32_t r = act ? qrow[wid][n2 - cnt + lane] : 0u;
+        uint32_t b = act ? qbr[wid][n2 - cnt + lane] : 0u;
+        n2 -= cnt;
+        bool pass = false;
+        if (act) {
+            uint32_t sidx = (uint32_t)(sk[r] - ssmin);
+            pass = sidx < ssint && ((sbits[sidx >> 5] >> (sidx & 31)) & 1u);
+        }
+        uint64_t m = __ballot(pass);
+        if (m) {
+            if (pass) {
+                uint32_t slot = QS - 1 - (n3 + __popcll(m & below));
+                qrow[wid][slot] = r;
+                qbr[wid][slot] = (uint16_t)b;
+            }
+            n3 += __popcll(m);
+            if (n3 >= 64 * B3) drain3(64 * B3);
+        }
+    };
+    // Q1: the top cnt entries; B == 0 confirms inline like pfq3
+    auto drain1 = [&](uint32_t cnt) {
+        bool act = lane < cnt;
+        int2 e = act ? q1[wid][n1 - cnt + lane] : make_int2(1, 0);
+        n1 -= cnt;
+        uint32_t brand1 = act ? pfirst[e.x - 1] : 0u; // exact category filter (0 = fail)
+        if constexpr (B == 0) {
+            if (!brand1) return;
+            uint32_t r = (uint32_t)e.y;
+            uint32_t sidx = (uint32_t)(sk[r] - ssmin);
+            if (sidx >= ssint || !((sbits[sidx >> 5] >> (sidx & 31)) & 1u)) return;
+            uint32_t year1 = dfirst[od[r] - dmin];
+            atomicAdd(&g[(year1 - 1) * 1000 + (brand1 - 1)],
+                      (unsigned long long)(int64_t)rv[r]);
+        } else {
+            uint64_t m = __ballot(brand1 != 0);
+            if (m) {
+                if (brand1) {
+                    uint32_t slot = n2 + __popcll(m & below);
+                    qrow[wid][slot] = (uint32_t)e.y;
+                    qbr[wid][slot] = (uint16_t)brand1;
+                }
+                n2 += __popcll(m);
+                if (n2 >= 64) drain2(64);
+            }
+        }
+    };
+    auto push = [&](int32_t key, uint32_t row, bool inb) {
+        uint32_t idx = (uint32_t)(key - psmin);
+        bool in = inb & (idx < psint);
+        uint32_t ia = (in ? idx : 0u) & ((1u << 18) - 1);
+        uint32_t ib = ((in ? idx : 0u) * 2654435761u) >> 14;
+        bool maybe = in & (pfa[ia >> 5] >> (ia & 31)) & (pfb[ib >> 5] >> (ib & 31)) & 1u;
+        uint64_t m = __ballot(maybe);
+        if (m) {
+            if (maybe) q1[wid][n1 + __popcll(m & below)] = make_int2(key, (int32_t)row);
+            n1 += __popcll(m);
+            if (n1 >= 64) drain1(64);
+        }
+    };
+    auto ld4nt = [&](const int4* p, uint64_t i) {
+        const uint64_t* q = (const uint64_t*)(p + i);
+        uint64_t lo = __builtin_nontemporal_load(q);
+        uint64_t hi = __builtin_nontemporal_load(q + 1);
+        int4 v;
+        v.x = (int32_t)lo; v.y = (int32_t)(lo >> 32);
+        v.z = (int32_t)hi; v.w = (int32_t)(hi >> 32);
+        return v;
+    };
+    uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (uint64_t)wid * WAVE;
+    uint64_t i = base + lane;
+    if constexpr (PREFETCH) {
+        // a pair is loaded only once its full-wave iteration is known to
+        // run, so every prefetched pair is consumed here and the remainder
+        // loop below starts where pfq3's would
+        bool more = base + stride + WAVE <= n4;
+        int4 pa = make_int4(0, 0, 0, 0), pb_ = pa;
+        if (more) {
+            pa = ld4nt(pk4, i);
+            pb_ = ld4nt(pk4, i + stride);
+        }
+        while (more) {
+            const uint64_t ci = i, ci2 = i + stride;
+            base += 2 * stride;
+            i += 2 * stride;
+            more = base + stride + WAVE <= n4;
+            int4 na = pa, nb = pb_;
+            if (more) {
+                na = ld4nt(pk4, i);
+                nb = ld4nt(pk4, i + stride);
+            }
+            #pragma unroll
+            for (int j = 0; j < 4; j++) push((&pa.x)[j], (uint32_t)(ci * 4 + j), true);
+            #pragma unroll
+            for (int j = 0; j < 4; j++) push((&pb_.x)[j], (uint32_t)(ci2 * 4 + j), true);
+            pa = na;
+            pb_ = nb;
+        }
+    } else {
+        for (; base + stride + WAVE <= n4; base += 2 * stride, i += 2 * stride) {
+            int4 pa = ld4nt(pk4, i);
+            uint64_t i2 = i + stride;
+            int4 pb_ = ld4nt(pk4, i2);
+            #pragma unroll
+            for (int j = 0; j < 4; j++) push((&pa.x)[j], (uint32_t)(i * 4 + j), true);
+            #pragma unroll
+            for (int j = 0; j < 4; j++) push((&pb_.x)[j], (uint32_t)(i2 * 4 + j), true);
+        }
+    }
+    for (; base < n4; base += stride, i += stride) {
+        bool inb = i < n4;
+        int4 p4 = inb ? pk4[i] : make_int4(0, 0, 0, 0);
+        #pragma unroll
+        for (int j = 0; j < 4; j++) push((&p4.x)[j], (uint32_t)(i * 4 + j), inb);
+    }
+    // final flush, in stage order: each partial drain leaves the next stage
+    // below its threshold again before that stage's own partial drain
+    if (n1 > 0) drain1(n1);
+    if constexpr (B > 0) {
+        if (n2 > 0) drain2(n2);
+        if (n3 > 0) drain3(n3);
+    }
+    // scalar row tail (n % 4): exact path
+    uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t r = n4 * 4 + tid; r < n; r += stride) {
+        uint32_t idx = (uint32_t)(pk[r] - psmin);
+        if (idx >= psint) continue;
+        uint32_t brand1 = pfirst[pk[r] - 1];
+        if (!brand1) continue;
+        uint32_t sidx = (uint32_t)(sk[r] - ssmin);
+        if (sidx >= ssint || !((sbits[sidx >> 5] >> (sidx & 31)) & 1u)) continue;
+        uint32_t year1 = dfirst[od[r] - dmin];
+        atomicAdd(&g[(year1 - 1) * 1000 + (brand1 - 1)], (unsigned long long)(int64_t)rv[r]);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < NG_Q21; j += blockDim.x)
+        if (g[j] != 0) atomicAdd(&group_sums[j], g[j]);
+}
+
+// ---------------------------------------------------------------------------
 // Two-stream pipelined q21 (GPUE_Q21_PIPE=1): the fused kernel's streaming
 // leg (1.57 ms) and its part-probe gather leg (2.32 ms) measured fully
 // ADDITIVE (profiles/q21_decomp.log) — so split them into an operator pair
@@ -4904,12 +5131,18 @@ int gpue_q21_star_agg_async(gpue_session* s, gpue_join_table* parts, gpue_join_t
     HIP_CHECK(hipMemsetAsync(group_sums->ptr, 0, NG_Q21 * sizeof(int64_t), s->stream));
     if (q21_pf() && parts->prefilter) {
         const char* e = getenv("GPUE_Q21_PF");
-        int mode = e ? atoi(e) : 7; // deferred-load default (the q43 form:
-                                    // stream pk only, drain sk/od/rv on
-                                    // demand): 1.106-1.133 vs mode 6's
-                                    // 1.559-1.560 ms interleaved (r02 late).
-                                    // 6 = full-stream + split fold; 4 =
-                                    // single-fold wave-queue; 1 = prefilter
+        int mode = e ? atoi(e) : 8; // staged cascade + prefetched pk stream
+                                    // over mode 7's deferred loads: 1.015-
+                                    // 1.040 (median 1.027) vs mode 7's 1.105-
+                                    // 1.132 (median 1.109) ms/step, 5 runs
+                                    // each interleaved at 2000 steps
+                                    // (profiles/r03_q21_cascade_ab.log).
+                                    // 7 = deferred loads (the q43 form: stream
+                                    // pk only, drain sk/od/rv on demand):
+                                    // 1.106-1.133 vs mode 6's 1.559-1.560 ms
+                                    // (r02 late). 6 = full-stream + split
+                                    // fold; 4 = single-fold wave-queue; 1 =
+                                    // prefilter
         // NT streams measured 2.267 vs 2.575 ms (frac 0.54 vs 0.47,
         // gpurun_out/q21_var_sweep.log r02) — default on; the global-group
         // 2-block variant (mode 2) measured 3.2 ms and stays for evidence
@@ -4931,7 +5164,34 @@ int gpue_q21_star_agg_async(gpue_session* s, gpue_join_table* parts, gpue_join_t
                                dates->first16, dates->min_key,
                                (unsigned long long*)group_sums->ptr);
         };
-        if (mode == 7) { // deferred-load (q43-form) experiment
+        // modes 7 and 8 queue row ids as 32 bits
+        ARG_CHECK((mode != 7 && mode != 8) || n <= UINT32_MAX);
+        if (mode == 8) { // staged cascade + prefetched pk stream
+            // GPUE_Q21_PF8_VAR, read per call: tens digit = PREFETCH, ones
+            // digit = B of k_q21_star_agg_pfq4 (10 = prefetch only, 1 =
+            // cascade only, 11 / 12 = both at B = 1 / 2). Medians of 5
+            // interleaved runs: 10 = 1.078, 1 = 1.034, 11 = 1.027, 12 =
+            // 1.030 ms/step against mode 7's 1.109, so 11 is the default
+            auto launch8 = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(env_cap("GPUE_GRID_PF", def_grid)),
+                                   dim3(tpb), 0, s->stream, (const int32_t*)pk->ptr,
+                                   (const int32_t*)sk->ptr, (const int32_t*)od->ptr,
+                                   (const int32_t*)rv->ptr, n, parts->prefilter2,
+                                   parts->set_min,
+                                   (uint64_t)(parts->set_max - parts->set_min + 1),
+                                   parts->first16, supps->bitset, supps->set_min,
+                                   (uint64_t)(supps->set_max - supps->set_min + 1),
+                                   dates->first16, dates->min_key,
+                                   (unsigned long long*)group_sums->ptr);
+            };
+            int var = (int)env_cap("GPUE_Q21_PF8_VAR", 11);
+            ARG_CHECK(var == 10 || var == 1 || var == 11 || var == 12);
+            if (var == 10) launch8(k_q21_star_agg_pfq4<true, 0>);
+            else if (var == 1) launch8(k_q21_star_agg_pfq4<false, 1>);
+            else if (var == 11) launch8(k_q21_star_agg_pfq4<true, 1>);
+            else launch8(k_q21_star_agg_pfq4<true, 2>);
+        }
+        else if (mode == 7) { // deferred-load (q43-form) experiment
             hipLaunchKernelGGL(k_q21_star_agg_pfq3, dim3(env_cap("GPUE_GRID_PF", def_grid)),
                                dim3(tpb), 0, s->stream, (const int32_t*)pk->ptr,
                                (const int32_t*)sk->ptr, (const int32_t*)od->ptr,
