@@ -125,6 +125,105 @@ int gpue_eval_conjuncts_i64(gpue_session* s, gpue_dbuf** cols, int n_cols, uint6
                             const int64_t* pred_lo, const int64_t* pred_hi, int n_preds,
                             uint64_t* out_rows);
 
+/* ---- predicate expressions ----
+ * Replaces ChunkPredicateEvaluator::eval_conjuncts over compound, IN and null
+ * predicates (reference be/src/exprs/chunk_predicate_evaluator.cpp:31-80 with
+ * compound_predicate / in_const_predicate / is_null_predicate children) plus
+ * Column::filter_range: a whole OR/NOT/IN/IS NULL tree over int32 and int64
+ * columns, nullable or not, is evaluated in ONE pass into a selection bitmap
+ * (gpue_pred_eval_mask); gpue_mask_compact then compacts any columns by a
+ * bitmap. The reference's per-conjunct u8 Filter vector shrinks to one bit
+ * per row; gpue_eval_conjuncts_* and gpue_scan_filter_* are unchanged.
+ *
+ * The program is postfix (reverse Polish) over parallel arrays (op, col, a,
+ * b), the convention gpue_eval_conjuncts_* uses for its predicates. A leaf
+ * pushes one value, a connective pops its operands and pushes the result; the
+ * root is the one value left.
+ *
+ * Semantics are SQL three-valued logic — what the reference's evaluator
+ * yields once a nullable result column is folded into the filter (filter =
+ * data & !null). An I32 column value is sign-extended to int64 and compared
+ * against a / b as int64 (so col < 2^40 on an I32 column is TRUE for every
+ * non-NULL row); all compares are signed. A compare, BETWEEN or IN leaf on a
+ * NULL row is UNKNOWN; with GPUE_P_RHS_COL it is UNKNOWN if either side is
+ * NULL, and the two columns must have the same pred_type. IS_NULL is TRUE or
+ * FALSE, never UNKNOWN, and FALSE on a column without a null mask. The value
+ * stored under a NULL row is never read into the result. AND / OR / NOT are
+ * Kleene: AND is F if either operand is F, T if both are T, else U; OR is T
+ * if either is T, F if both are F, else U; NOT swaps T and F and keeps U. IN
+ * with b == 0 is FALSE on non-NULL rows, UNKNOWN on NULL rows; IN lists may be
+ * unsorted and hold duplicates (the host sorts and de-duplicates before
+ * upload). A row's bit is set iff the root is TRUE. mask holds ceil(n_rows/64)
+ * u64 words, bit (r & 63) of word r >> 6 = row r; bits of the last word at
+ * positions >= n_rows are written as 0. out_count = set bits.
+ *
+ * Strings are deliberately not a leaf type: a varchar predicate is lowered by
+ * the caller to EQ / IN / BETWEEN over dictionary codes (the engine already
+ * decodes dict pages to int32 codes, gpue_page_decode_*).
+ *
+ * GPUE_ERR_ARG, before any launch or allocation, for: n_insns outside
+ * 1..GPUE_PRED_MAX_INSNS; an unknown op; stack underflow; stack depth above
+ * GPUE_PRED_MAX_STACK; final stack depth other than 1; a column index out of
+ * range (the RHS_COL index in `a` included); an RHS_COL type mismatch; RHS_COL
+ * on a non-compare op; an IN range outside [0, n_in_values]; an unknown
+ * pred_type; n_rows >= 2^32; a column or null buffer shorter than n_rows
+ * elements; a mask shorter than ceil(n_rows/64)*8 bytes. n_rows == 0 returns
+ * GPUE_OK with count 0. */
+/* pred column types */
+#define GPUE_PT_I32 0
+#define GPUE_PT_I64 1
+/* leaf ops: push one value. `col` = predicate-column index. */
+#define GPUE_P_EQ 0   /* col == a */
+#define GPUE_P_NE 1
+#define GPUE_P_LT 2
+#define GPUE_P_LE 3
+#define GPUE_P_GT 4
+#define GPUE_P_GE 5
+#define GPUE_P_BETWEEN 6   /* a <= col <= b */
+#define GPUE_P_IN 7        /* col in in_values[a .. a+b) */
+#define GPUE_P_IS_NULL 8
+/* connectives: pop operands, push result */
+#define GPUE_P_AND 16
+#define GPUE_P_OR 17
+#define GPUE_P_NOT 18
+/* OR-ed into a compare op (EQ..GE): `a` is a second predicate-column index */
+#define GPUE_P_RHS_COL 0x100
+#define GPUE_PRED_MAX_INSNS 64
+#define GPUE_PRED_MAX_STACK 16
+int gpue_pred_eval_mask(gpue_session* s,
+                        gpue_dbuf** pred_cols,
+                        gpue_dbuf** pred_nulls, /* entries may be NULL; u8, nonzero = NULL row */
+                        const int32_t* pred_type, int n_pred_cols,
+                        const int32_t* insn_op, const int32_t* insn_col,
+                        const int64_t* insn_a, const int64_t* insn_b, int n_insns,
+                        const int64_t* in_values, /* host; may be NULL when n_in_values == 0 */
+                        uint64_t n_in_values,
+                        uint64_t n_rows,
+                        gpue_dbuf* mask,        /* ceil(n_rows/64) u64 words */
+                        uint64_t* out_count);
+/* Stable compaction of any columns by a bitmap in gpue_pred_eval_mask's
+ * format: survivors keep ascending row order, so the output is bit-identical
+ * to the reference's filter_range loop (be/src/base/simd/filter.h:26-38).
+ * Bits of the last word at positions >= n_rows are ignored even if the caller
+ * left garbage there. col_width is 1, 4 or 8 bytes per column — width 1 so a
+ * nullable column's u8 null mask travels with it. out_row_idx (nullable)
+ * receives the surviving row indices as ascending u32. With n_cols == 0 and
+ * out_row_idx == NULL the call is a count-only popcount of the mask.
+ * Two phases, no workgroup waits on another: per-tile popcounts, a block scan
+ * of the tile counts, then the emit. After the scan the count is known and
+ * *out_count is set; a dst_cols[k] shorter than count*width bytes or an
+ * out_row_idx shorter than count*4 bytes then returns GPUE_ERR_ARG with
+ * *out_count valid, so the caller can size and retry. GPUE_ERR_ARG also for
+ * src == dst for any column, any dst (or out_row_idx) overlapping a src, the
+ * mask or another dst of the same call, a width outside {1, 4, 8}, a src
+ * shorter than n_rows*width bytes, a mask shorter than ceil(n_rows/64)*8
+ * bytes, and n_rows >= 2^32. */
+int gpue_mask_compact(gpue_session* s, gpue_dbuf* mask, uint64_t n_rows,
+                      gpue_dbuf** src_cols, gpue_dbuf** dst_cols,
+                      const int32_t* col_width /* 1, 4 or 8 bytes */, int n_cols,
+                      gpue_dbuf* out_row_idx /* nullable; u32 surviving row indices, ascending */,
+                      uint64_t* out_count);
+
 /* ---- hash-join build ----
  * Replaces JoinHashTable::build with the RANGE_DIRECT_MAPPING method the
  * selector takes for dense int keys (reference

@@ -15,6 +15,8 @@
 #include <cstring>
 #include <cstdlib>
 #include <thread>
+#include <algorithm>
+#include <vector>
 #include "gpue.h"
 
 // ---------------------------------------------------------------------------
@@ -3060,6 +3062,550 @@ int gpue_eval_conjuncts_i64(gpue_session* s, gpue_dbuf** cols, int n_cols, uint6
     (void)hipFree(d_filter);
     (void)hipFree(d_tc);
     *out_rows = n;
+    return GPUE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Predicate expressions: a postfix OR/NOT/IN/IS NULL tree -> selection bitmap
+// (gpue_pred_eval_mask), then stable compaction of any columns by a bitmap
+// (gpue_mask_compact). DESIGN.md §4e; measured: §4b row "filter_expr".
+//
+// The per-conjunct path above restates a CPU cache idiom (one launch + one
+// count readback + one u8 filter byte per row PER CONJUNCT). Here the whole
+// tree is evaluated in registers in one pass over the predicate columns and
+// the reference's Filter vector shrinks to one bit per row.
+//
+// Layout (profiles/r02_filter_wl.log's wave-coalesced winner): a block tile is
+// PRED_TILE rows; each wave owns a contiguous PRED_WAVE_RUN rows of it and in
+// step j lane l handles row base + 64*j + l, so every load is a coalesced
+// 64-row run and the step's __ballot IS mask word (base >> 6) + j.
+//
+// The program is wave-uniform: it rides in the kernel-argument segment
+// (PredProgram, < 4 KB), so decode is scalar loads + uniform branches. The
+// evaluation stack is a shift register — two u32 per row (is-TRUE bits,
+// is-FALSE bits; UNKNOWN = neither) — never a runtime-indexed array, which
+// would go to scratch (the recorded negative at k_filter_lookback_pipe).
+// ---------------------------------------------------------------------------
+// 2 steps x 2048 blocks measured best on a 3-column tree (0.61 ms / 100 M rows
+// vs 0.79 at 4 steps, 0.76 at 8); one lone int64 leaf prefers 8 steps x 1024
+// blocks (0.20 vs 0.26 ms) but has its own specialised kernel
+static constexpr int PRED_STEPS = 2;                               // 64-row steps per wave run
+static constexpr int PRED_WAVE_RUN = WAVE * PRED_STEPS;            // 128 rows
+static constexpr int PRED_TILE = PRED_WAVE_RUN * (BLOCK / WAVE);   // 512 rows
+static constexpr uint32_t PRED_IN_LDS_CAP = 4096;                  // int64 values (32 KB)
+// a valid 64-insn program has at most 32 leaves, each naming <= 2 columns
+static constexpr int PRED_MAX_SLOTS = GPUE_PRED_MAX_INSNS;
+
+// meta: bits 0-7 op, 8-15 lhs slot, 16-23 rhs slot, 24 RHS_COL, 25 column is I64
+struct PredProgram {
+    const void* col[PRED_MAX_SLOTS];
+    const uint8_t* nul[PRED_MAX_SLOTS];
+    int64_t a[GPUE_PRED_MAX_INSNS];
+    int64_t b[GPUE_PRED_MAX_INSNS];
+    uint32_t meta[GPUE_PRED_MAX_INSNS];
+    int n_insns;
+};
+
+// branchless lower bound over a sorted, de-duplicated list: the trip count
+// depends only on len (wave-uniform), <= 32 iterations; every read is in
+// [0, len)
+template <typename ListPtr>
+__device__ static inline bool pred_in_list(ListPtr list, uint32_t len, int64_t v) {
+    if (len == 0) return false;
+    uint32_t lo = 0, m = len;
+    while (m > 1) {
+        uint32_t half = m >> 1;
+        lo += (list[lo + half - 1] < v) ? half : 0;
+        m -= half;
+    }
+    return list[lo] == v;
+}
+
+// One wave run: PRED_STEPS 64-row steps from row `base`. FULL = the whole run
+// lies below n, so no load is predicated and the PRED_STEPS loads of a leaf
+// issue back to back; the (at most one per wave) ragged run takes the
+// predicated form, where a lane at or beyond n never loads. Returns this
+// lane's mask word in `mine` (lane j holds the word of step j) and the run's
+// popcount.
+template <bool FULL, typename ListPtr>
+__device__ static __forceinline__ uint32_t
+pred_eval_run(const PredProgram& p, const int64_t* __restrict__ in_values, ListPtr s_in,
+              int in_lds, uint64_t base, uint64_t n, int lane, uint64_t& mine) {
+    uint32_t tb[PRED_STEPS], fb[PRED_STEPS];
+    bool act[PRED_STEPS];
+    const uint64_t row0 = base + lane;
+    #pragma unroll
+    for (int j = 0; j < PRED_STEPS; j++) {
+        tb[j] = fb[j] = 0;
+        act[j] = FULL || row0 + (uint64_t)j * WAVE < n;
+    }
+    for (int i = 0; i < p.n_insns; i++) {
+        const uint32_t m = p.meta[i];
+        const uint32_t op = m & 0xffu;
+        if (op == GPUE_P_NOT) {
+            #pragma unroll
+            for (int j = 0; j < PRED_STEPS; j++) {
+                uint32_t t0 = tb[j] & 1u, f0 = fb[j] & 1u;
+                tb[j] = (tb[j] & ~1u) | f0;
+                fb[j] = (fb[j] & ~1u) | t0;
+            }
+            continue;
+        }
+        if (op == GPUE_P_AND || op == GPUE_P_OR) {
+            #pragma unroll
+            for (int j = 0; j < PRED_STEPS; j++) {
+                uint32_t xt = tb[j] & 1u, yt = (tb[j] >> 1) & 1u;
+                uint32_t xf = fb[j] & 1u, yf = (fb[j] >> 1) & 1u;
+                uint32_t rt = op == GPUE_P_AND ? (xt & yt) : (xt | yt);
+                uint32_t rf = op == GPUE_P_AND ? (xf | yf) : (xf & yf);
+                tb[j] = ((tb[j] >> 2) << 1) | rt;
+                fb[j] = ((fb[j] >> 2) << 1) | rf;
+            }
+            continue;
+        }
+        // leaf: load the column (and its null mask) for all steps first so
+        // PRED_STEPS loads are in flight, then compare
+        const bool is64 = (m >> 25) & 1u, rhs = (m >> 24) & 1u;
+        const void* c0 = p.col[(m >> 8) & 0xffu];
+        const uint8_t* n0 = p.nul[(m >> 8) & 0xffu];
+        const int64_t a = p.a[i], b = p.b[i];
+        int64_t v[PRED_STEPS], w[PRED_STEPS];
+        bool isn[PRED_STEPS];
+        #pragma unroll
+        for (int j = 0; j < PRED_STEPS; j++) {
+            const uint64_t row = row0 + (uint64_t)j * WAVE;
+            v[j] = 0;
+            isn[j] = false;
+            if (act[j]) {
+                if (n0) isn[j] = n0[row] != 0;
+                v[j] = is64 ? ((const int64_t*)c0)[row] : (int64_t)((const int32_t*)c0)[row];
+            }
+            w[j] = a;
+        }
+        if (rhs) {
+            const void* c1 = p.col[(m >> 16) & 0xffu];
+            const uint8_t* n1 = p.nul[(m >> 16) & 0xffu];
+            #pragma unroll
+            for (int j = 0; j < PRED_STEPS; j++) {
+                const uint64_t row = row0 + (uint64_t)j * WAVE;
+                if (act[j]) {
+                    if (n1) isn[j] = isn[j] || n1[row] != 0;
+                    w[j] = is64 ? ((const int64_t*)c1)[row] : (int64_t)((const int32_t*)c1)[row];
+                }
+            }
+        }
+        #pragma unroll
+        for (int j = 0; j < PRED_STEPS; j++) {
+            bool r, known = !isn[j];
+            switch (op) {
+            case GPUE_P_EQ: r = v[j] == w[j]; break;
+            case GPUE_P_NE: r = v[j] != w[j]; break;
+            case GPUE_P_LT: r = v[j] < w[j]; break;
+            case GPUE_P_LE: r = v[j] <= w[j]; break;
+            case GPUE_P_GT: r = v[j] > w[j]; break;
+            case GPUE_P_GE: r = v[j] >= w[j]; break;
+            case GPUE_P_BETWEEN: r = v[j] >= a && v[j] <= b; break;
+            case GPUE_P_IN:
+                r = in_lds ? pred_in_list(s_in + a, (uint32_t)b, v[j])
+                           : pred_in_list(in_values + a, (uint32_t)b, v[j]);
+                break;
+            default: /* GPUE_P_IS_NULL: TRUE or FALSE, never UNKNOWN */
+                r = isn[j];
+                known = true;
+                break;
+            }
+            tb[j] = (tb[j] << 1) | (uint32_t)(known && r);
+            fb[j] = (fb[j] << 1) | (uint32_t)(known && !r);
+        }
+    }
+    // the step's ballot is its mask word
+    uint32_t cnt = 0;
+    mine = 0;
+    #pragma unroll
+    for (int j = 0; j < PRED_STEPS; j++) {
+        uint64_t word = __ballot(act[j] && (tb[j] & 1u));
+        cnt += __popcll(word);
+        if (lane == j) mine = word;
+    }
+    return cnt;
+}
+
+__global__ __launch_bounds__(BLOCK) void
+k_pred_eval_mask(const PredProgram p, const int64_t* __restrict__ in_values, uint32_t n_in,
+                 int in_lds, uint64_t n, uint64_t n_tiles, uint64_t* __restrict__ mask,
+                 unsigned long long* __restrict__ count) {
+    extern __shared__ int64_t s_in[];
+    if (in_lds) {
+        for (uint32_t i = threadIdx.x; i < n_in; i += BLOCK) s_in[i] = in_values[i];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    const uint64_t n_words = (n + 63) >> 6;
+    unsigned long long wave_count = 0;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t base = t * PRED_TILE + (uint64_t)wid * PRED_WAVE_RUN;
+        if (base >= n) continue; // wave-uniform; no barrier inside this loop
+        uint64_t mine;
+        if (base + PRED_WAVE_RUN <= n)
+            wave_count += pred_eval_run<true>(p, in_values, s_in, in_lds, base, n,
+                                                          lane, mine);
+        else
+            wave_count += pred_eval_run<false>(p, in_values, s_in, in_lds, base, n,
+                                                           lane, mine);
+        // lanes 0..PRED_STEPS-1 store the run's words side by side (one store
+        // per word, coalesced)
+        const uint64_t widx = (base >> 6) + lane;
+        if (lane < PRED_STEPS && widx < n_words) mask[widx] = mine;
+    }
+    if (lane == 0 && wave_count) atomicAdd(count, wave_count);
+}
+
+// frees its device pointer on every return path of the two entries below
+struct PredTmp {
+    void* p = nullptr;
+    ~PredTmp() { if (p) (void)hipFree(p); }
+};
+
+int gpue_pred_eval_mask(gpue_session* s, gpue_dbuf** pred_cols, gpue_dbuf** pred_nulls,
+                        const int32_t* pred_type, int n_pred_cols, const int32_t* insn_op,
+                        const int32_t* insn_col, const int64_t* insn_a, const int64_t* insn_b,
+                        int n_insns, const int64_t* in_values, uint64_t n_in_values,
+                        uint64_t n_rows, gpue_dbuf* mask, uint64_t* out_count) {
+    ARG_CHECK(s && pred_cols && pred_type && insn_op && insn_col && insn_a && insn_b &&
+              mask && out_count);
+    ARG_CHECK(n_pred_cols >= 1);
+    ARG_CHECK(n_insns >= 1 && n_insns <= GPUE_PRED_MAX_INSNS);
+    ARG_CHECK(n_rows < (1ull << 32));
+    ARG_CHECK(in_values || n_in_values == 0);
+    const uint64_t n_words = (n_rows + 63) >> 6;
+    ARG_CHECK(mask->bytes >= n_words * 8);
+    for (int c = 0; c < n_pred_cols; c++) {
+        ARG_CHECK(pred_type[c] == GPUE_PT_I32 || pred_type[c] == GPUE_PT_I64);
+        ARG_CHECK(pred_cols[c] != nullptr);
+        ARG_CHECK(pred_cols[c]->bytes >= n_rows * (pred_type[c] == GPUE_PT_I64 ? 8 : 4));
+        if (pred_nulls && pred_nulls[c]) ARG_CHECK(pred_nulls[c]->bytes >= n_rows);
+    }
+    // ---- validate the program and lower it to PredProgram (host only) ----
+    PredProgram p;
+    memset(&p, 0, sizeof(p));
+    p.n_insns = n_insns;
+    int slot_col[PRED_MAX_SLOTS];
+    int n_slots = 0;
+    auto slot_of = [&](int c) -> int {
+        for (int k = 0; k < n_slots; k++)
+            if (slot_col[k] == c) return k;
+        if (n_slots == PRED_MAX_SLOTS) return -1;
+        slot_col[n_slots] = c;
+        p.col[n_slots] = pred_cols[c]->ptr;
+        p.nul[n_slots] = (pred_nulls && pred_nulls[c]) ? (const uint8_t*)pred_nulls[c]->ptr
+                                                        : nullptr;
+        return n_slots++;
+    };
+    std::vector<int64_t> lists; // every IN list sorted + de-duplicated, back to back
+    int depth = 0;
+    for (int i = 0; i < n_insns; i++) {
+        const int32_t raw = insn_op[i];
+        const int32_t op = raw & ~GPUE_P_RHS_COL;
+        const bool rhs = (raw & GPUE_P_RHS_COL) != 0;
+        if (op == GPUE_P_AND || op == GPUE_P_OR || op == GPUE_P_NOT) {
+            ARG_CHECK(!rhs);
+            ARG_CHECK(depth >= (op == GPUE_P_NOT ? 1 : 2)); // stack underflow
+            if (op != GPUE_P_NOT) depth--;
+            p.meta[i] = (uint32_t)op;
+            continue;
+        }
+        ARG_CHECK(op >= GPUE_P_EQ && op <= GPUE_P_IS_NULL); // unknown op
+        ARG_CHECK(!rhs || op <= GPUE_P_GE);                 // RHS_COL on a non-compare op
+        const int32_t c = insn_col[i];
+        ARG_CHECK(c >= 0 && c < n_pred_cols);
+        ARG_CHECK(++depth <= GPUE_PRED_MAX_STACK);
+        const int s0 = slot_of(c);
+        ARG_CHECK(s0 >= 0);
+        int s1 = 0;
+        p.a[i] = insn_a[i];
+        p.b[i] = insn_b[i];
+        if (rhs) {
+            const int64_t c2 = insn_a[i];
+            ARG_CHECK(c2 >= 0 && c2 < n_pred_cols);
+            ARG_CHECK(pred_type[c2] == pred_type[c]); // RHS_COL type mismatch
+            s1 = slot_of((int)c2);
+            ARG_CHECK(s1 >= 0);
+            p.a[i] = 0;
+        }
+        if (op == GPUE_P_IN) {
+            const int64_t off = insn_a[i], len = insn_b[i];
+            ARG_CHECK(off >= 0 && len >= 0 && (uint64_t)off <= n_in_values &&
+                      (uint64_t)len <= n_in_values - (uint64_t)off);
+            std::vector<int64_t> l(in_values + off, in_values + off + len);
+            std::sort(l.begin(), l.end());
+            l.erase(std::unique(l.begin(), l.end()), l.end());
+            p.a[i] = (int64_t)lists.size();
+            p.b[i] = (int64_t)l.size();
+            lists.insert(lists.end(), l.begin(), l.end());
+        }
+        p.meta[i] = (uint32_t)op | ((uint32_t)s0 << 8) | ((uint32_t)s1 << 16) |
+                    (rhs ? 1u << 24 : 0u) | (pred_type[c] == GPUE_PT_I64 ? 1u << 25 : 0u);
+    }
+    ARG_CHECK(depth == 1); // the root, and nothing else, is left on the stack
+    *out_count = 0;
+    if (n_rows == 0) return GPUE_OK;
+
+    // one device block: [count u64 | IN lists]
+    const uint32_t n_in = (uint32_t)lists.size();
+    PredTmp tmp;
+    HIP_CHECK(hipMalloc(&tmp.p, 8 + (uint64_t)n_in * 8));
+    unsigned long long* d_count = (unsigned long long*)tmp.p;
+    const int64_t* d_in = (const int64_t*)((char*)tmp.p + 8);
+    HIP_CHECK(hipMemsetAsync(d_count, 0, 8, s->stream));
+    if (n_in)
+        HIP_CHECK(hipMemcpyAsync((void*)d_in, lists.data(), (uint64_t)n_in * 8,
+                                 hipMemcpyHostToDevice, s->stream));
+    const int in_lds = n_in > 0 && n_in <= PRED_IN_LDS_CAP;
+    const uint64_t n_tiles = (n_rows + PRED_TILE - 1) / PRED_TILE;
+    const uint32_t nb = (uint32_t)(n_tiles < MAX_GRID ? n_tiles : MAX_GRID);
+    hipLaunchKernelGGL(k_pred_eval_mask, dim3(nb), dim3(BLOCK), in_lds ? n_in * 8 : 0,
+                       s->stream, p, d_in, n_in, in_lds, n_rows, n_tiles,
+                       (uint64_t*)mask->ptr, d_count);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(s->pinned, d_count, 8, hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream)); // `lists` stays alive until here
+    *out_count = *(const uint64_t*)s->pinned;
+    return GPUE_OK;
+}
+
+// ---- gpue_mask_compact: popcount per tile -> block scan -> emit ----------
+// A compaction tile is MC_TILE_WORDS mask words (8192 rows): 2^32 rows are
+// 2^19 tiles, which one 1024-thread block scans in one launch. No kernel
+// waits on another workgroup (no lookback): the scan sits between two
+// launches. Bits at positions >= n_rows are masked off in both phases.
+static constexpr int MC_TILE_WORDS = 128;
+static constexpr int MC_TILE_ROWS = MC_TILE_WORDS * 64;               // 8192
+static constexpr int MC_WAVE_WORDS = MC_TILE_WORDS / (BLOCK / WAVE);  // 32 steps per wave
+static constexpr int MC_SCAN_TPB = 1024;
+static constexpr int MC_MAX_COLS = 8; // columns per emit launch
+static constexpr int MC_GROUP = 8; // 64-row steps whose loads are issued together in the emit
+static constexpr uint64_t MC_COUNT_GRID = 256; // blocks of the count pass (4 tiles each)
+
+__device__ static inline uint64_t mc_load_word(const uint64_t* __restrict__ mask,
+                                               uint64_t widx, uint64_t n_words, uint64_t n) {
+    if (widx >= n_words) return 0;
+    uint64_t wv = mask[widx];
+    if (widx == n_words - 1 && (n & 63)) wv &= (1ull << (n & 63)) - 1; // caller's tail garbage
+    return wv;
+}
+
+// one wave per tile
+__global__ __launch_bounds__(BLOCK) void
+k_mask_tile_counts(const uint64_t* __restrict__ mask, uint64_t n, uint32_t n_tiles,
+                   uint32_t* __restrict__ tile_counts) {
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    const uint64_t n_words = (n + 63) >> 6;
+    const uint32_t waves = gridDim.x * (BLOCK / WAVE);
+    for (uint32_t t = blockIdx.x * (BLOCK / WAVE) + wid; t < n_tiles; t += waves) {
+        const uint64_t w0 = (uint64_t)t * MC_TILE_WORDS;
+        uint32_t c = __popcll(mc_load_word(mask, w0 + lane, n_words, n)) +
+                     __popcll(mc_load_word(mask, w0 + WAVE + lane, n_words, n));
+        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, WAVE);
+        if (lane == 0) tile_counts[t] = c;
+    }
+}
+
+// single-block exclusive scan of n tile counts into offs[0..n] (offs[n] =
+// total): each thread sums a contiguous run, the block scans the 1024 run
+// sums (wave shuffles + one LDS hop), each thread replays its run
+__global__ __launch_bounds__(MC_SCAN_TPB) void
+k_mask_scan_tiles(const uint32_t* __restrict__ counts, uint32_t n,
+                  uint64_t* __restrict__ offs) {
+    __shared__ uint64_t wsum[MC_SCAN_TPB / WAVE];
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    const uint32_t per = (n + MC_SCAN_TPB - 1) / MC_SCAN_TPB;
+    const uint64_t lo64 = (uint64_t)threadIdx.x * per;
+    const uint32_t lo = lo64 < n ? (uint32_t)lo64 : n;
+    const uint32_t hi = lo64 + per < n ? (uint32_t)(lo64 + per) : n;
+    uint64_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += counts[i];
+    uint64_t inc = sum;
+    for (int off = 1; off < WAVE; off <<= 1) {
+        uint64_t o = __shfl_up(inc, off, WAVE);
+        if (lane >= off) inc += o;
+    }
+    if (lane == WAVE - 1) wsum[wid] = inc;
+    __syncthreads();
+    if (wid == 0) {
+        uint64_t v = lane < MC_SCAN_TPB / WAVE ? wsum[lane] : 0, vi = v;
+        for (int off = 1; off < MC_SCAN_TPB / WAVE; off <<= 1) {
+            uint64_t o = __shfl_up(vi, off, WAVE);
+            if (lane >= off) vi += o;
+        }
+        if (lane < MC_SCAN_TPB / WAVE) wsum[lane] = vi - v;
+    }
+    __syncthreads();
+    uint64_t run = wsum[wid] + inc - sum;
+    for (uint32_t i = lo; i < hi; i++) {
+        offs[i] = run;
+        run += counts[i];
+    }
+    if (threadIdx.x == MC_SCAN_TPB - 1) offs[n] = run;
+}
+
+struct McCols {
+    const void* src[MC_MAX_COLS];
+    void* dst[MC_MAX_COLS];
+    int width[MC_MAX_COLS];
+    int n_cols;
+};
+
+template <typename T>
+__device__ static __forceinline__ void
+mc_move_group(const void* src, void* dst, uint64_t row0, uint64_t tile_base,
+              const bool (&bit)[MC_GROUP], const uint32_t (&off)[MC_GROUP]) {
+    T v[MC_GROUP];
+    #pragma unroll
+    for (int g = 0; g < MC_GROUP; g++)
+        if (bit[g]) v[g] = ((const T*)src)[row0 + 64 * g];
+    #pragma unroll
+    for (int g = 0; g < MC_GROUP; g++)
+        if (bit[g]) ((T*)dst)[tile_base + off[g]] = v[g];
+}
+
+// block per tile, wave w owns words [32w, 32w+32) of it. Every wave scans the
+// tile's 128 word popcounts itself (1 KB of L1/L2 hits), so no barrier and no
+// LDS: per 64-row step the position is word prefix + popc(word & lanes_below).
+__global__ __launch_bounds__(BLOCK) void
+k_mask_emit(const uint64_t* __restrict__ mask, uint64_t n, uint32_t n_tiles,
+            const uint64_t* __restrict__ tile_offs, const McCols cols,
+            uint32_t* __restrict__ row_idx) {
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    const uint64_t n_words = (n + 63) >> 6;
+    const uint64_t below = (1ull << lane) - 1;
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t w0 = (uint64_t)t * MC_TILE_WORDS;
+        const uint64_t m0 = mc_load_word(mask, w0 + lane, n_words, n);
+        const uint64_t m1 = mc_load_word(mask, w0 + WAVE + lane, n_words, n);
+        const uint32_t c0 = __popcll(m0), c1 = __popcll(m1);
+        uint32_t i0 = c0, i1 = c1; // inclusive wave scans
+        for (int off = 1; off < WAVE; off <<= 1) {
+            uint32_t o0 = __shfl_up(i0, off, WAVE), o1 = __shfl_up(i1, off, WAVE);
+            if (lane >= off) { i0 += o0; i1 += o1; }
+        }
+        const uint32_t e0 = i0 - c0;                               // word prefix, words 0..63
+        const uint32_t e1 = i1 - c1 + __shfl(i0, WAVE - 1, WAVE);  // words 64..127
+        const uint64_t tile_base = tile_offs[t];
+        // MC_GROUP steps at a time: all of a group's loads issue before its
+        // first store, so a wave keeps MC_GROUP gathers in flight instead of one
+        for (int j0 = 0; j0 < MC_WAVE_WORDS; j0 += MC_GROUP) {
+            const int wi0 = wid * MC_WAVE_WORDS + j0; // wave-uniform
+            bool bit[MC_GROUP];
+            uint32_t off[MC_GROUP];
+            bool any = false;
+            #pragma unroll
+            for (int g = 0; g < MC_GROUP; g++) {
+                const int wi = wi0 + g;
+                const uint64_t word = wi < WAVE ? __shfl(m0, wi, WAVE)
+                                                : __shfl(m1, wi - WAVE, WAVE);
+                const uint32_t ex = wi < WAVE ? __shfl(e0, wi, WAVE)
+                                              : __shfl(e1, wi - WAVE, WAVE);
+                bit[g] = (word >> lane) & 1;
+                off[g] = ex + __popcll(word & below);
+                any = any || word != 0;
+            }
+            if (!any) continue; // wave-uniform
+            // set bits sit below n (mc_load_word), so row0 + 64 g < n where bit[g]
+            const uint64_t row0 = (w0 + wi0) * 64 + lane;
+            if (row_idx) {
+                #pragma unroll
+                for (int g = 0; g < MC_GROUP; g++)
+                    if (bit[g]) row_idx[tile_base + off[g]] = (uint32_t)(row0 + 64 * g);
+            }
+            #pragma unroll
+            for (int k = 0; k < MC_MAX_COLS; k++) {
+                if (k < cols.n_cols) {
+                    if (cols.width[k] == 8)
+                        mc_move_group<uint64_t>(cols.src[k], cols.dst[k], row0, tile_base, bit, off);
+                    else if (cols.width[k] == 4)
+                        mc_move_group<uint32_t>(cols.src[k], cols.dst[k], row0, tile_base, bit, off);
+                    else
+                        mc_move_group<uint8_t>(cols.src[k], cols.dst[k], row0, tile_base, bit, off);
+                }
+            }
+        }
+    }
+}
+
+int gpue_mask_compact(gpue_session* s, gpue_dbuf* mask, uint64_t n_rows, gpue_dbuf** src_cols,
+                      gpue_dbuf** dst_cols, const int32_t* col_width, int n_cols,
+                      gpue_dbuf* out_row_idx, uint64_t* out_count) {
+    ARG_CHECK(s && mask && out_count && n_cols >= 0);
+    ARG_CHECK(n_cols == 0 || (src_cols && dst_cols && col_width));
+    ARG_CHECK(n_rows < (1ull << 32));
+    const uint64_t n_words = (n_rows + 63) >> 6;
+    ARG_CHECK(mask->bytes >= n_words * 8);
+    auto overlap = [](const gpue_dbuf* x, const gpue_dbuf* y) {
+        const char *xa = (const char*)x->ptr, *ya = (const char*)y->ptr;
+        return xa < ya + y->bytes && ya < xa + x->bytes;
+    };
+    for (int k = 0; k < n_cols; k++) {
+        ARG_CHECK(col_width[k] == 1 || col_width[k] == 4 || col_width[k] == 8);
+        ARG_CHECK(src_cols[k] && dst_cols[k]);
+        ARG_CHECK(src_cols[k]->bytes >= n_rows * (uint64_t)col_width[k]);
+    }
+    for (int k = 0; k < n_cols; k++) {
+        ARG_CHECK(!overlap(dst_cols[k], mask));
+        if (out_row_idx) ARG_CHECK(!overlap(dst_cols[k], out_row_idx));
+        for (int j = 0; j < n_cols; j++) {
+            ARG_CHECK(!overlap(dst_cols[k], src_cols[j])); // src == dst, or dst over any src
+            if (j != k) ARG_CHECK(!overlap(dst_cols[k], dst_cols[j]));
+        }
+    }
+    if (out_row_idx) {
+        ARG_CHECK(!overlap(out_row_idx, mask));
+        for (int j = 0; j < n_cols; j++) ARG_CHECK(!overlap(out_row_idx, src_cols[j]));
+    }
+    *out_count = 0;
+    if (n_rows == 0) return GPUE_OK;
+
+    const uint32_t n_tiles = (uint32_t)((n_rows + MC_TILE_ROWS - 1) / MC_TILE_ROWS);
+    // one device block: [tile_offs u64 x (n_tiles+1) | tile_counts u32 x n_tiles]
+    PredTmp tmp;
+    HIP_CHECK(hipMalloc(&tmp.p, ((uint64_t)n_tiles + 1) * 8 + (uint64_t)n_tiles * 4));
+    uint64_t* d_offs = (uint64_t*)tmp.p;
+    uint32_t* d_counts = (uint32_t*)(d_offs + n_tiles + 1);
+    // the count pass reads 1 bit per row: a streaming-sized grid is plenty
+    const uint32_t nb_count = (uint32_t)std::min<uint64_t>(
+        (n_tiles + BLOCK / WAVE - 1) / (BLOCK / WAVE), MC_COUNT_GRID);
+    hipLaunchKernelGGL(k_mask_tile_counts, dim3(nb_count), dim3(BLOCK), 0, s->stream,
+                       (const uint64_t*)mask->ptr, n_rows, n_tiles, d_counts);
+    hipLaunchKernelGGL(k_mask_scan_tiles, dim3(1), dim3(MC_SCAN_TPB), 0, s->stream, d_counts,
+                       n_tiles, d_offs);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(s->pinned, d_offs + n_tiles, 8, hipMemcpyDeviceToHost,
+                             s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    const uint64_t count = *(const uint64_t*)s->pinned;
+    *out_count = count; // set before the size checks so the caller can size and retry
+    for (int k = 0; k < n_cols; k++)
+        ARG_CHECK(dst_cols[k]->bytes >= count * (uint64_t)col_width[k]);
+    if (out_row_idx) ARG_CHECK(out_row_idx->bytes >= count * 4);
+    if (count == 0 || (n_cols == 0 && !out_row_idx)) return GPUE_OK;
+
+    const uint32_t nb_emit = (uint32_t)std::min<uint64_t>(n_tiles, MAX_GRID);
+    int k0 = 0;
+    do { // MC_MAX_COLS columns per launch; the row indexes ride with the first
+        McCols mc;
+        memset(&mc, 0, sizeof(mc));
+        for (; k0 < n_cols && mc.n_cols < MC_MAX_COLS; k0++, mc.n_cols++) {
+            mc.src[mc.n_cols] = src_cols[k0]->ptr;
+            mc.dst[mc.n_cols] = dst_cols[k0]->ptr;
+            mc.width[mc.n_cols] = col_width[k0];
+        }
+        hipLaunchKernelGGL(k_mask_emit, dim3(nb_emit), dim3(BLOCK), 0, s->stream,
+                           (const uint64_t*)mask->ptr, n_rows, n_tiles,
+                           (const uint64_t*)d_offs, mc,
+                           out_row_idx ? (uint32_t*)out_row_idx->ptr : nullptr);
+        out_row_idx = nullptr;
+    } while (k0 < n_cols);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s->stream));
     return GPUE_OK;
 }
 

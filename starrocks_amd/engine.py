@@ -85,6 +85,12 @@ def _declare(lib):
         "gpue_eval_conjuncts_i64": (c_i32, [c_vp, ctypes.POINTER(c_vp), c_i32, c_u64,
                                             c_vp, c_vp, c_vp, c_vp, c_i32,
                                             ctypes.POINTER(c_u64)]),
+        "gpue_pred_eval_mask": (c_i32, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                        c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32,
+                                        c_vp, c_u64, c_u64, c_vp, ctypes.POINTER(c_u64)]),
+        "gpue_mask_compact": (c_i32, [c_vp, c_vp, c_u64, ctypes.POINTER(c_vp),
+                                      ctypes.POINTER(c_vp), c_vp, c_i32, c_vp,
+                                      ctypes.POINTER(c_u64)]),
         "gpue_scan_filter_i64_lt": (c_i32, [c_vp, c_vp, c_u64, c_i64, c_vp, ctypes.POINTER(c_u64)]),
         "gpue_scan_filter_i64_lt_sp": (c_i32, [c_vp, c_vp, c_u64, c_i64, c_vp, ctypes.POINTER(c_u64)]),
         "gpue_join_build_payload_i32": (c_i32, [c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_vp)]),
@@ -378,6 +384,81 @@ class Engine:
             po.ctypes.data_as(c_vp), pl.ctypes.data_as(c_vp), ph.ctypes.data_as(c_vp),
             len(preds), ctypes.byref(out)))
         return out.value
+
+    # --- predicate expressions (gpue.h "predicate expressions") ---
+    PT_I32, PT_I64 = 0, 1
+
+    def pred_eval_mask(self, pred_cols, program, n_rows, mask: DBuf) -> int:
+        """Evaluate a compiled predicate (predicate.compile_predicate) over
+        pred_cols = [(DBuf, nulls DBuf or None, PT_I32 / PT_I64), ...] into
+        the selection bitmap `mask` (ceil(n_rows/64) u64 words; bit r & 63 of
+        word r >> 6 = row r); returns the number of selected rows."""
+        op, col, a, b, in_values = program
+        op = np.ascontiguousarray(op, np.int32)
+        col = np.ascontiguousarray(col, np.int32)
+        a = np.ascontiguousarray(a, np.int64)
+        b = np.ascontiguousarray(b, np.int64)
+        in_values = np.ascontiguousarray(in_values, np.int64)
+        if not (len(op) == len(col) == len(a) == len(b)):
+            raise ValueError("program arrays differ in length")
+        nc = len(pred_cols)
+        cols = (c_vp * max(nc, 1))(*[c[0]._h for c in pred_cols])
+        nulls = (c_vp * max(nc, 1))(*[c[1]._h if c[1] is not None else None
+                                      for c in pred_cols])
+        types = np.array([c[2] for c in pred_cols], np.int32)
+        cnt = c_u64()
+        _ck(self._lib, self._lib.gpue_pred_eval_mask(
+            self._h, cols, nulls, types.ctypes.data_as(c_vp), nc,
+            op.ctypes.data_as(c_vp), col.ctypes.data_as(c_vp), a.ctypes.data_as(c_vp),
+            b.ctypes.data_as(c_vp), len(op),
+            in_values.ctypes.data_as(c_vp) if len(in_values) else None, len(in_values),
+            n_rows, mask._h, ctypes.byref(cnt)))
+        return cnt.value
+
+    def mask_compact(self, mask: DBuf, n_rows, cols, out_row_idx: DBuf = None) -> int:
+        """Stable compaction by a selection bitmap. cols = [(src DBuf, dst
+        DBuf, width 1 / 4 / 8), ...]; out_row_idx (optional) receives the
+        surviving u32 row indices. cols == [] and no out_row_idx is a
+        count-only popcount. Returns the number of survivors; a dst too short
+        for it raises GpueError whose .needed_count is that number."""
+        nc = len(cols)
+        src = (c_vp * max(nc, 1))(*[c[0]._h for c in cols])
+        dst = (c_vp * max(nc, 1))(*[c[1]._h for c in cols])
+        widths = np.array([c[2] for c in cols], np.int32)
+        cnt = c_u64()
+        try:
+            _ck(self._lib, self._lib.gpue_mask_compact(
+                self._h, mask._h, n_rows, src, dst, widths.ctypes.data_as(c_vp), nc,
+                out_row_idx._h if out_row_idx is not None else None, ctypes.byref(cnt)))
+        except GpueError as e:
+            e.needed_count = cnt.value
+            raise
+        return cnt.value
+
+    def filter_expr(self, tree, pred_cols, payload_cols, n_rows):
+        """One-shot WHERE: mask, exact-size allocation, compact. pred_cols as
+        pred_eval_mask (predicate column i of `tree` = pred_cols[i]);
+        payload_cols = [(DBuf, width), ...]. Returns ([new DBuf per payload
+        column, exactly count*width bytes (1 byte when count is 0)], count);
+        the inputs are left alone."""
+        from starrocks_amd.predicate import compile_predicate
+        program = compile_predicate(tree, [c[2] for c in pred_cols])
+        mask = self.alloc(max((n_rows + 63) // 64, 1) * 8)
+        out = []
+        try:
+            cnt = self.pred_eval_mask(pred_cols, program, n_rows, mask)
+            for _, w in payload_cols:
+                out.append(self.alloc(max(cnt * w, 1)))
+            got = self.mask_compact(mask, n_rows, [(src, dst, w) for (src, w), dst
+                                                   in zip(payload_cols, out)])
+            assert got == cnt
+        except BaseException:
+            for b in out:
+                b.free()
+            raise
+        finally:
+            mask.free()
+        return out, cnt
 
     # --- JoinHashMapSelector restatement (join_hash_table.cpp:164-344) ---
     JM_NAMES = {0: "DIRECT", 1: "RANGE_DIRECT", 2: "RANGE_DIRECT_SET",

@@ -543,6 +543,73 @@ class TopNSinkOperator(Operator):
         return out
 
 
+class FilterOperator(Operator):
+    """WHERE as a pass-through operator — the ChunkPredicateEvaluator::
+    eval_conjuncts + Chunk::filter step of the reference's scan / filter
+    operators, for a whole predicate tree (starrocks_amd/predicate.py forms:
+    and / or / not / cmp / cmp_col / between / in / is_null, SQL three-valued
+    logic).
+
+    Chunks are {"n": rows, "cols": [DBuf, ...]}. pred_col_map[i] = (chunk
+    column index, chunk column index of its u8 null mask or None, type 0
+    int32 / 1 int64) binds predicate column i of the tree; col_widths[k] is
+    the byte width (1, 4 or 8) of chunk column k — a nullable column's null
+    mask is just another width-1 chunk column, so it is compacted with its
+    values. The tree is compiled once, at construction.
+
+    Per pushed chunk: one pred_eval_mask pass over the predicate columns into
+    a 1-bit-per-row mask, exact-size output columns, one mask_compact over
+    every chunk column; the input columns are freed. One chunk in, one chunk
+    out (possibly with n == 0), rows in their input order.
+
+    Uses only engine.alloc / pred_eval_mask / mask_compact and DBuf.free, so
+    it runs against a numpy stand-in engine without a GPU."""
+
+    def __init__(self, engine, tree, pred_col_map, col_widths):
+        super().__init__()
+        from starrocks_amd.predicate import compile_predicate
+        self._e = engine
+        self._map = [(int(c), None if nl is None else int(nl), int(t))
+                     for c, nl, t in pred_col_map]
+        self._widths = [int(w) for w in col_widths]
+        if any(w not in (1, 4, 8) for w in self._widths):
+            raise ValueError("column widths must be 1, 4 or 8 bytes")
+        for c, nl, t in self._map:
+            if not 0 <= c < len(self._widths) or self._widths[c] != (8 if t == 1 else 4):
+                raise ValueError(f"predicate column {c} does not match its declared type")
+            if nl is not None and (not 0 <= nl < len(self._widths) or self._widths[nl] != 1):
+                raise ValueError(f"null mask column {nl} must be a width-1 chunk column")
+        self._program = compile_predicate(tree, [t for _, _, t in self._map])
+        self._out = None
+        self.rows_in = 0
+        self.rows_out = 0
+
+    def need_input(self):
+        return self._out is None and not self._finishing
+
+    def has_output(self):
+        return self._out is not None
+
+    def push_chunk(self, chunk):
+        n, cols = chunk["n"], chunk["cols"]
+        assert len(cols) == len(self._widths)
+        mask = self._e.alloc(max((n + 63) // 64, 1) * 8)
+        pred_cols = [(cols[c], None if nl is None else cols[nl], t) for c, nl, t in self._map]
+        cnt = self._e.pred_eval_mask(pred_cols, self._program, n, mask)
+        out = [self._e.alloc(max(cnt * w, 1)) for w in self._widths]
+        got = self._e.mask_compact(mask, n, list(zip(cols, out, self._widths)))
+        assert got == cnt
+        for b in (mask, *cols):
+            b.free()
+        self.rows_in += n
+        self.rows_out += cnt
+        self._out = {"n": cnt, "cols": out}
+
+    def pull_chunk(self):
+        c, self._out = self._out, None
+        return c
+
+
 def q1_operator_pipeline(engine, seed, total_rows, year=1993,
                          chunk_rows=DEFAULT_CHUNK_ROWS, dim_chunk_rows=1000):
     """Config-2's plan as the reference would run it — dim source -> build
