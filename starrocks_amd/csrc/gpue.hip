@@ -11,11 +11,14 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC \
 //          -I../../include gpue.hip -o ../libgpue.so
 #include <hip/hip_runtime.h>
+#include <cassert>
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
 #include <thread>
 #include <algorithm>
+#include <memory>
+#include <type_traits>
 #include <vector>
 #include "gpue.h"
 
@@ -170,6 +173,12 @@ struct gpue_join_table {
     uint64_t* build_keys64 = nullptr; // BUCKET_CHAINED64: 8-byte build keys
     ulonglong2* build_keys128 = nullptr; // BUCKET_CHAINED128: 16-byte build keys
 };
+
+// a table under construction: a build that fails releases what it allocated
+struct JoinTableDeleter {
+    void operator()(gpue_join_table* t) const { gpue_join_table_destroy(t); }
+};
+using JoinTableOwner = std::unique_ptr<gpue_join_table, JoinTableDeleter>;
 
 int gpue_device_count(int* out) {
     int n = 0;
@@ -741,6 +750,134 @@ __global__ void k_scan_small(uint64_t* data, uint32_t n) {
         }
         data[n] = acc; // total
     }
+}
+
+// exclusive scan of u32 counts into u64 offsets — per-tile sums, the thread-0
+// scan above over the tile sums, then a per-tile add. Correctness-first:
+// test-path sizes (≤ tens of M rows), not the bench hot loop.
+__global__ void k_block_sums_u32(const uint32_t* __restrict__ v, uint64_t n, uint64_t tile,
+                                 uint64_t* __restrict__ sums) {
+    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
+    uint64_t c = 0;
+    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) c += v[i];
+    for (int off = WAVE / 2; off > 0; off >>= 1)
+        c += __shfl_down((unsigned long long)c, off, WAVE);
+    __shared__ uint64_t wsum[BLOCK / WAVE];
+    int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    if (lane == 0) wsum[wid] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+        for (int w = 0; w < BLOCK / WAVE; w++) t += wsum[w];
+        sums[blockIdx.x] = t;
+    }
+}
+
+__global__ void k_scan_offsets(const uint32_t* __restrict__ counts, uint64_t n, uint64_t tile,
+                               const uint64_t* __restrict__ block_offsets,
+                               uint64_t* __restrict__ offsets) {
+    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
+    if (threadIdx.x == 0) {
+        uint64_t acc = block_offsets[blockIdx.x];
+        for (uint64_t i = lo; i < hi; i++) {
+            offsets[i] = acc;
+            acc += counts[i];
+        }
+    }
+}
+
+// owns a driver's temporary device buffers: every return path frees them
+struct DevScratch {
+    static constexpr int CAP = 8;
+    void* ptrs[CAP];
+    int n = 0;
+    DevScratch() = default;
+    DevScratch(const DevScratch&) = delete;
+    DevScratch& operator=(const DevScratch&) = delete;
+    ~DevScratch() {
+        while (n) (void)hipFree(ptrs[--n]);
+    }
+    template <class T>
+    hipError_t alloc(T** out, uint64_t bytes) {
+        assert(n < CAP && "DevScratch is full: raise CAP"); // a coding error, not a device OOM
+        if (n == CAP) return hipErrorInvalidValue;
+        hipError_t e = hipMalloc(out, bytes);
+        if (e == hipSuccess) ptrs[n++] = *out;
+        return e;
+    }
+};
+
+// The u32-counts -> u64-offsets scan of every two-phase (count, then emit)
+// driver, in the two steps the callers split at: total() reduces the counts
+// to their u64 sum, which a caller without output buffers returns as is;
+// offsets() then writes the exclusive per-row offsets. init() sizes the scan
+// for n counts and allocates its tile sums; callers run it before they
+// enqueue the kernel that produces the counts, so no allocation lands while
+// that kernel runs. The only place that launches k_block_sums_u32 /
+// k_scan_offsets.
+struct CountScan {
+    gpue_session* s = nullptr;
+    const uint32_t* d_counts = nullptr;
+    uint64_t n = 0, tile = 0;
+    uint32_t nb = 0;
+    uint64_t* d_bsums = nullptr; // nb tile offsets, then the total
+
+    int init(gpue_session* s_, DevScratch& tmp, uint64_t n_) {
+        s = s_;
+        n = n_;
+        nb = grid_for(n);
+        tile = (n + nb - 1) / nb;
+        HIP_CHECK(tmp.alloc(&d_bsums, (nb + 1) * sizeof(uint64_t)));
+        return GPUE_OK;
+    }
+    int total(const uint32_t* counts, uint64_t* out) {
+        d_counts = counts;
+        hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts, n,
+                           tile, d_bsums);
+        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
+        HIP_CHECK(hipMemcpyAsync(out, d_total(), sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                 s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        return GPUE_OK;
+    }
+    const uint64_t* d_total() const { return d_bsums + nb; }
+    void offsets(uint64_t* d_offsets) const { // d_offsets: n entries
+        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts, n,
+                           tile, d_bsums, d_offsets);
+    }
+};
+
+// Two-phase probe protocol shared by every generic probe entry: count per
+// probe row -> total (returned alone when there are no output buffers) ->
+// offsets -> emit the (probe row, build row) pairs, ordered by probe row.
+// launch_count(nb, d_counts) and launch_emit(nb, d_counts, d_offsets,
+// out_probe, out_build) enqueue the two kernels on s->stream.
+template <class LaunchCount, class LaunchEmit>
+static int probe_count_scan_emit(gpue_session* s, uint64_t n_rows, gpue_dbuf* out_probe_idx,
+                                 gpue_dbuf* out_build_idx, uint64_t* match_count,
+                                 LaunchCount launch_count, LaunchEmit launch_emit) {
+    DevScratch tmp;
+    CountScan scan;
+    uint32_t* d_counts = nullptr;
+    uint64_t* d_offsets = nullptr;
+    uint32_t nb = grid_for(n_rows);
+    HIP_CHECK(tmp.alloc(&d_counts, (n_rows ? n_rows : 1) * sizeof(uint32_t)));
+    int rc = scan.init(s, tmp, n_rows);
+    if (rc != GPUE_OK) return rc;
+    launch_count(nb, d_counts);
+    uint64_t total = 0;
+    rc = scan.total(d_counts, &total);
+    if (rc != GPUE_OK) return rc;
+    *match_count = total;
+    if (out_probe_idx && out_build_idx && total > 0) {
+        ARG_CHECK(out_probe_idx->bytes >= total * 4 && out_build_idx->bytes >= total * 4);
+        HIP_CHECK(tmp.alloc(&d_offsets, n_rows * sizeof(uint64_t)));
+        scan.offsets(d_offsets);
+        launch_emit(nb, (const uint32_t*)d_counts, (const uint64_t*)d_offsets,
+                    (uint32_t*)out_probe_idx->ptr, (uint32_t*)out_build_idx->ptr);
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+    }
+    return GPUE_OK;
 }
 
 __global__ void k_filter_emit(const int64_t* __restrict__ in, uint64_t n, int64_t theta,
@@ -1590,7 +1727,8 @@ int gpue_join_build_payload_i32(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* pay
     if (rc != GPUE_OK) return rc;
     uint64_t interval = (uint64_t)(mx - mn + 1);
     ARG_CHECK(interval < (1ull << 32)); // selector's RANGE_DIRECT gate (join_hash_table.cpp:287)
-    gpue_join_table* t = new gpue_join_table();
+    JoinTableOwner own(new gpue_join_table());
+    gpue_join_table* t = own.get();
     t->s = s; t->min_key = mn; t->max_key = mx;
     t->bucket_size = interval; t->row_count = n_rows;
     HIP_CHECK(hipMalloc(&t->first, interval * sizeof(uint32_t)));
@@ -1602,8 +1740,9 @@ int gpue_join_build_payload_i32(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* pay
     // derive the probe-side structures: set bounds first,
     // then the bitset over just the passing keys' bounding range
     int32_t h_bounds[2] = {INT32_MAX, INT32_MIN};
+    DevScratch tmp;
     int32_t* d_bounds = nullptr;
-    HIP_CHECK(hipMalloc(&d_bounds, 2 * sizeof(int32_t)));
+    HIP_CHECK(tmp.alloc(&d_bounds, 2 * sizeof(int32_t)));
     HIP_CHECK(hipMemcpyAsync(d_bounds, h_bounds, sizeof(h_bounds), hipMemcpyHostToDevice,
                              s->stream));
     hipLaunchKernelGGL(k_set_bounds, dim3(grid_for(interval)), dim3(BLOCK), 0, s->stream,
@@ -1611,7 +1750,6 @@ int gpue_join_build_payload_i32(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* pay
     HIP_CHECK(hipMemcpyAsync(h_bounds, d_bounds, sizeof(h_bounds), hipMemcpyDeviceToHost,
                              s->stream));
     HIP_CHECK(hipStreamSynchronize(s->stream));
-    (void)hipFree(d_bounds);
     uint64_t set_off, set_interval;
     if (h_bounds[0] > h_bounds[1]) { // empty pass set
         t->set_min = mn;
@@ -1641,7 +1779,7 @@ int gpue_join_build_payload_i32(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* pay
     hipLaunchKernelGGL(k_build_prefilter_split_w, dim3(grid_for(set_interval)), dim3(BLOCK),
                        0, s->stream, t->bitset, set_interval, t->prefilter2w);
     uint32_t* d_ovf = nullptr;
-    HIP_CHECK(hipMalloc(&d_ovf, sizeof(uint32_t)));
+    HIP_CHECK(tmp.alloc(&d_ovf, sizeof(uint32_t)));
     HIP_CHECK(hipMemsetAsync(d_ovf, 0, sizeof(uint32_t), s->stream));
     HIP_CHECK(hipMalloc(&t->first16, interval * sizeof(uint16_t)));
     hipLaunchKernelGGL(k_derive_u16, dim3(grid_for(interval)), dim3(BLOCK), 0, s->stream,
@@ -1649,9 +1787,8 @@ int gpue_join_build_payload_i32(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* pay
     uint32_t ovf = 0;
     HIP_CHECK(hipMemcpyAsync(&ovf, d_ovf, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_CHECK(hipStreamSynchronize(s->stream));
-    (void)hipFree(d_ovf);
     if (ovf) { (void)hipFree(t->first16); t->first16 = nullptr; }
-    *out = t;
+    *out = own.release();
     return GPUE_OK;
 }
 
@@ -1665,7 +1802,8 @@ int gpue_join_build_range_direct_i32(gpue_session* s, gpue_dbuf* keys, uint64_t 
     if (rc != GPUE_OK) return rc;
     uint64_t interval = (uint64_t)(mx - mn + 1);
     ARG_CHECK(interval < (1ull << 32));
-    gpue_join_table* t = new gpue_join_table();
+    JoinTableOwner own(new gpue_join_table());
+    gpue_join_table* t = own.get();
     t->s = s; t->min_key = mn; t->max_key = mx;
     t->bucket_size = interval; t->row_count = row_count;
     t->kind = gpue_join_table::RANGE_DIRECT;
@@ -1676,7 +1814,7 @@ int gpue_join_build_range_direct_i32(gpue_session* s, gpue_dbuf* keys, uint64_t 
     hipLaunchKernelGGL(k_build_range_direct, dim3(grid_for(row_count)), dim3(BLOCK), 0,
                        s->stream, (const int32_t*)keys->ptr, row_count, mn, t->first, t->next);
     HIP_CHECK(hipGetLastError());
-    *out = t;
+    *out = own.release();
     return GPUE_OK;
 }
 
@@ -1725,15 +1863,6 @@ __device__ static inline uint32_t join_hash_u32(uint32_t v, uint32_t num_log_buc
     return (v * 2654435761u) >> (32 - num_log_buckets);
 }
 
-__global__ void k_build_bucket_chained(const uint32_t* __restrict__ keys, uint64_t row_count,
-                                       uint32_t log_bucket_size, uint32_t* __restrict__ first,
-                                       uint32_t* __restrict__ next) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = 1 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= row_count;
-         i += stride)
-        next[i] = atomicExch(&first[join_hash_u32(keys[i], log_bucket_size)], (uint32_t)i);
-}
-
 // 8-byte (BIGINT) key variants — JoinKeyHash<8> (join_hash_map_helper.h:
 // 46-55, multiplier 11400714819323198485; pinned by the oracle's stats64
 // KATs), same chained structure with u64 build-key compares.
@@ -1742,81 +1871,35 @@ __device__ static inline uint32_t join_hash_u64_dev(uint64_t v, uint32_t num_log
     return (uint32_t)((v * 11400714819323198485ull) >> (64 - num_log_buckets));
 }
 
-__global__ void k_build_bucket_chained64(const uint64_t* __restrict__ keys,
-                                         uint64_t row_count, uint32_t log_bucket_size,
-                                         uint32_t* __restrict__ first,
-                                         uint32_t* __restrict__ next) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = 1 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= row_count;
-         i += stride)
-        next[i] = atomicExch(&first[join_hash_u64_dev(keys[i], log_bucket_size)],
-                             (uint32_t)i);
-}
-
-__global__ void k_probe_count_bc64(const uint64_t* __restrict__ probe_keys, uint64_t n,
-                                   uint32_t log_bucket_size,
-                                   const uint32_t* __restrict__ first,
-                                   const uint32_t* __restrict__ next,
-                                   const uint64_t* __restrict__ build_keys, int mode,
-                                   uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint64_t k = probe_keys[i];
-        uint32_t b = first[join_hash_u64_dev(k, log_bucket_size)];
-        uint32_t c = 0;
-        while (b != 0) {
-            c += (build_keys[b] == k);
-            b = next[b];
-        }
-        row_counts[i] = join_mode_count(c, mode);
+// key -> bucket per key width, as a value the build and probe kernels take
+struct HashU32 {
+    uint32_t log_bucket_size;
+    static HashU32 of(const gpue_join_table* t) { return {t->log_bucket_size}; }
+    __device__ uint32_t operator()(uint32_t k) const {
+        return join_hash_u32(k, log_bucket_size);
     }
-}
-
-__global__ void k_probe_emit_bc64(const uint64_t* __restrict__ probe_keys, uint64_t n,
-                                  uint32_t log_bucket_size,
-                                  const uint32_t* __restrict__ first,
-                                  const uint32_t* __restrict__ next,
-                                  const uint64_t* __restrict__ build_keys, int mode,
-                                  const uint32_t* __restrict__ row_counts,
-                                  const uint64_t* __restrict__ row_offsets,
-                                  uint32_t* __restrict__ out_probe,
-                                  uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (row_counts[i] == 0) continue;
-        uint64_t pos = row_offsets[i];
-        uint64_t k = probe_keys[i];
-        uint32_t b = first[join_hash_u64_dev(k, log_bucket_size)];
-        uint32_t c = 0;
-        while (b != 0) {
-            if (build_keys[b] == k) {
-                if (mode == 0 || mode == 3 || (mode == 1 && c == 0)) {
-                    out_probe[pos] = (uint32_t)i;
-                    out_build[pos] = b;
-                    pos++;
-                }
-                c++;
-                if (mode == 1 || mode == 2) break;
-            }
-            b = next[b];
-        }
-        if (c == 0 && (mode == 2 || mode == 3)) {
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = 0;
-        }
+};
+struct HashU64 {
+    uint32_t log_bucket_size;
+    static HashU64 of(const gpue_join_table* t) { return {t->log_bucket_size}; }
+    __device__ uint32_t operator()(uint64_t k) const {
+        return join_hash_u64_dev(k, log_bucket_size);
     }
-}
+};
 
-__global__ void k_build_bucket_chained_nulls(const uint32_t* __restrict__ keys,
-                                             const uint8_t* __restrict__ is_nulls,
-                                             uint64_t row_count, uint32_t log_bucket_size,
-                                             uint32_t* __restrict__ first,
-                                             uint32_t* __restrict__ next) {
+// the chain scatter for every fixed-width key; NULLS drops flagged build rows
+template <class K, class H, bool NULLS>
+__global__ void k_build_bucket_chained(const K* __restrict__ keys,
+                                       const uint8_t* __restrict__ is_nulls,
+                                       uint64_t row_count, H hash,
+                                       uint32_t* __restrict__ first,
+                                       uint32_t* __restrict__ next) {
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = 1 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= row_count;
          i += stride) {
-        if (is_nulls[i]) continue; // null build rows never enter a chain
-        next[i] = atomicExch(&first[join_hash_u32(keys[i], log_bucket_size)], (uint32_t)i);
+        if (NULLS && is_nulls[i]) continue; // null build rows never enter a chain
+        const K k = keys[i]; // one load of the whole key; the 16-byte crc hashes the copy
+        next[i] = atomicExch(&first[hash(k)], (uint32_t)i);
     }
 }
 
@@ -1953,73 +2036,43 @@ int gpue_join_select_method(int key_constructor, int lt_class, uint64_t row_coun
     return GPUE_JM_BUCKET_CHAINED; // fallback :258-263 (asof out of scope)
 }
 
-extern "C" int gpue_join_build_bucket_chained_nulls_u32(gpue_session* s, gpue_dbuf* keys,
-                                                        gpue_dbuf* is_nulls,
-                                                        uint64_t row_count,
-                                                        gpue_join_table** out);
-int gpue_join_build_bucket_chained_nulls_u32(gpue_session* s, gpue_dbuf* keys,
-                                             gpue_dbuf* is_nulls, uint64_t row_count,
-                                             gpue_join_table** out) {
-    ARG_CHECK(s && keys && is_nulls && out && row_count > 0 && row_count + 1 < (1ull << 31));
-    ARG_CHECK(keys->bytes >= (row_count + 1) * 4 && is_nulls->bytes >= row_count + 1);
-    gpue_join_table* t = new gpue_join_table();
+// The bucket-chained build for every fixed-width key: copy the keys next to
+// the table (the probe compares against them), then scatter the chains.
+// `build_keys` names the table member of that key width; is_nulls is read only
+// when NULLS (today the u32 entry alone; a nullable wider key passes true).
+template <class K, class H, bool NULLS = false>
+static int build_bucket_chained(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* is_nulls,
+                                uint64_t row_count, gpue_join_table::Kind kind,
+                                K* gpue_join_table::*build_keys, gpue_join_table** out) {
+    JoinTableOwner own(new gpue_join_table());
+    gpue_join_table* t = own.get();
     t->s = s;
-    t->kind = gpue_join_table::BUCKET_CHAINED;
+    t->kind = kind;
     t->row_count = row_count;
     t->bucket_size = calc_bucket_size((uint32_t)(row_count + 1));
     t->log_bucket_size = (uint32_t)__builtin_ctzll(t->bucket_size);
     HIP_CHECK(hipMalloc(&t->first, t->bucket_size * sizeof(uint32_t)));
     HIP_CHECK(hipMalloc(&t->next, (row_count + 1) * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&t->build_keys, (row_count + 1) * sizeof(uint32_t)));
+    HIP_CHECK(hipMalloc(&(t->*build_keys), (row_count + 1) * sizeof(K)));
     HIP_CHECK(hipMemsetAsync(t->first, 0, t->bucket_size * sizeof(uint32_t), s->stream));
     HIP_CHECK(hipMemsetAsync(t->next, 0, (row_count + 1) * sizeof(uint32_t), s->stream));
-    HIP_CHECK(hipMemcpyAsync(t->build_keys, keys->ptr, (row_count + 1) * sizeof(uint32_t),
+    HIP_CHECK(hipMemcpyAsync(t->*build_keys, keys->ptr, (row_count + 1) * sizeof(K),
                              hipMemcpyDeviceToDevice, s->stream));
-    hipLaunchKernelGGL(k_build_bucket_chained_nulls, dim3(grid_for(row_count)), dim3(BLOCK),
-                       0, s->stream, t->build_keys, (const uint8_t*)is_nulls->ptr, row_count,
-                       t->log_bucket_size, t->first, t->next);
+    hipLaunchKernelGGL((k_build_bucket_chained<K, H, NULLS>), dim3(grid_for(row_count)),
+                       dim3(BLOCK), 0, s->stream, t->*build_keys,
+                       NULLS ? (const uint8_t*)is_nulls->ptr : nullptr, row_count, H::of(t),
+                       t->first, t->next);
     HIP_CHECK(hipGetLastError());
-    *out = t;
+    *out = own.release();
     return GPUE_OK;
 }
-
-extern "C" int gpue_join_build_bucket_chained_u32(gpue_session* s, gpue_dbuf* keys,
-                                                  uint64_t row_count, gpue_join_table** out);
-int gpue_join_build_bucket_chained_u32(gpue_session* s, gpue_dbuf* keys, uint64_t row_count,
-                                       gpue_join_table** out) {
-    ARG_CHECK(s && keys && out && row_count > 0 && row_count + 1 < (1ull << 31));
-    ARG_CHECK(keys->bytes >= (row_count + 1) * 4);
-    gpue_join_table* t = new gpue_join_table();
-    t->s = s;
-    t->kind = gpue_join_table::BUCKET_CHAINED;
-    t->row_count = row_count;
-    t->bucket_size = calc_bucket_size((uint32_t)(row_count + 1));
-    t->log_bucket_size = (uint32_t)__builtin_ctzll(t->bucket_size);
-    HIP_CHECK(hipMalloc(&t->first, t->bucket_size * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&t->next, (row_count + 1) * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&t->build_keys, (row_count + 1) * sizeof(uint32_t)));
-    HIP_CHECK(hipMemsetAsync(t->first, 0, t->bucket_size * sizeof(uint32_t), s->stream));
-    HIP_CHECK(hipMemsetAsync(t->next, 0, (row_count + 1) * sizeof(uint32_t), s->stream));
-    HIP_CHECK(hipMemcpyAsync(t->build_keys, keys->ptr, (row_count + 1) * sizeof(uint32_t),
-                             hipMemcpyDeviceToDevice, s->stream));
-    hipLaunchKernelGGL(k_build_bucket_chained, dim3(grid_for(row_count)), dim3(BLOCK), 0,
-                       s->stream, t->build_keys, row_count, t->log_bucket_size, t->first,
-                       t->next);
-    HIP_CHECK(hipGetLastError());
-    *out = t;
-    return GPUE_OK;
-}
-
-// forward decls: the count->scan->emit helpers are defined with the probe
-// section further down this file
-__global__ void k_block_sums_u32(const uint32_t* __restrict__ counts, uint64_t n,
-                                 uint64_t tile, uint64_t* __restrict__ block_sums);
-__global__ void k_scan_small(uint64_t* __restrict__ sums, uint64_t n_blocks);
-__global__ void k_scan_offsets(const uint32_t* __restrict__ counts, uint64_t n, uint64_t tile,
-                               const uint64_t* __restrict__ block_offsets,
-                               uint64_t* __restrict__ offsets);
 
 extern "C" {
+int gpue_join_build_bucket_chained_nulls_u32(gpue_session* s, gpue_dbuf* keys,
+                                             gpue_dbuf* is_nulls, uint64_t row_count,
+                                             gpue_join_table** out);
+int gpue_join_build_bucket_chained_u32(gpue_session* s, gpue_dbuf* keys, uint64_t row_count,
+                                       gpue_join_table** out);
 int gpue_join_build_bucket_chained_u64(gpue_session* s, gpue_dbuf* keys /*u64, 1-based*/,
                                        uint64_t row_count, gpue_join_table** out);
 int gpue_join_probe_emit_mode_u64(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
@@ -2027,70 +2080,32 @@ int gpue_join_probe_emit_mode_u64(gpue_session* s, gpue_join_table* t, gpue_dbuf
                                   gpue_dbuf* out_build_idx, uint64_t* match_count);
 }
 
+int gpue_join_build_bucket_chained_nulls_u32(gpue_session* s, gpue_dbuf* keys,
+                                             gpue_dbuf* is_nulls, uint64_t row_count,
+                                             gpue_join_table** out) {
+    ARG_CHECK(s && keys && is_nulls && out && row_count > 0 && row_count + 1 < (1ull << 31));
+    ARG_CHECK(keys->bytes >= (row_count + 1) * 4 && is_nulls->bytes >= row_count + 1);
+    return build_bucket_chained<uint32_t, HashU32, true>(s, keys, is_nulls, row_count,
+                                                         gpue_join_table::BUCKET_CHAINED,
+                                                         &gpue_join_table::build_keys, out);
+}
+
+int gpue_join_build_bucket_chained_u32(gpue_session* s, gpue_dbuf* keys, uint64_t row_count,
+                                       gpue_join_table** out) {
+    ARG_CHECK(s && keys && out && row_count > 0 && row_count + 1 < (1ull << 31));
+    ARG_CHECK(keys->bytes >= (row_count + 1) * 4);
+    return build_bucket_chained<uint32_t, HashU32>(s, keys, nullptr, row_count,
+                                                   gpue_join_table::BUCKET_CHAINED,
+                                                   &gpue_join_table::build_keys, out);
+}
+
 int gpue_join_build_bucket_chained_u64(gpue_session* s, gpue_dbuf* keys, uint64_t row_count,
                                        gpue_join_table** out) {
     ARG_CHECK(s && keys && out && row_count > 0 && row_count + 1 < (1ull << 31));
     ARG_CHECK(keys->bytes >= (row_count + 1) * 8);
-    gpue_join_table* t = new gpue_join_table();
-    t->s = s;
-    t->kind = gpue_join_table::BUCKET_CHAINED64;
-    t->row_count = row_count;
-    t->bucket_size = calc_bucket_size((uint32_t)(row_count + 1));
-    t->log_bucket_size = (uint32_t)__builtin_ctzll(t->bucket_size);
-    HIP_CHECK(hipMalloc(&t->first, t->bucket_size * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&t->next, (row_count + 1) * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&t->build_keys64, (row_count + 1) * sizeof(uint64_t)));
-    HIP_CHECK(hipMemsetAsync(t->first, 0, t->bucket_size * sizeof(uint32_t), s->stream));
-    HIP_CHECK(hipMemsetAsync(t->next, 0, (row_count + 1) * sizeof(uint32_t), s->stream));
-    HIP_CHECK(hipMemcpyAsync(t->build_keys64, keys->ptr, (row_count + 1) * sizeof(uint64_t),
-                             hipMemcpyDeviceToDevice, s->stream));
-    hipLaunchKernelGGL(k_build_bucket_chained64, dim3(grid_for(row_count)), dim3(BLOCK), 0,
-                       s->stream, t->build_keys64, row_count, t->log_bucket_size, t->first,
-                       t->next);
-    HIP_CHECK(hipGetLastError());
-    *out = t;
-    return GPUE_OK;
-}
-
-int gpue_join_probe_emit_mode_u64(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
-                                  uint64_t n_rows, int mode, gpue_dbuf* out_probe_idx,
-                                  gpue_dbuf* out_build_idx, uint64_t* match_count) {
-    ARG_CHECK(s && t && probe_keys && match_count);
-    ARG_CHECK(t->kind == gpue_join_table::BUCKET_CHAINED64);
-    ARG_CHECK(mode >= 0 && mode <= 3);
-    ARG_CHECK(probe_keys->bytes >= n_rows * 8);
-    uint32_t nb = grid_for(n_rows);
-    uint64_t tile = (n_rows + nb - 1) / nb;
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bsums = nullptr;
-    uint64_t* d_offsets = nullptr;
-    HIP_CHECK(hipMalloc(&d_counts, n_rows * 4));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * 8));
-    hipLaunchKernelGGL(k_probe_count_bc64, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint64_t*)probe_keys->ptr, n_rows, t->log_bucket_size,
-                       t->first, t->next, t->build_keys64, mode, d_counts);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                       n_rows, tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    *match_count = total;
-    if (out_probe_idx && out_build_idx && total > 0) {
-        ARG_CHECK(out_probe_idx->bytes >= total * 4 && out_build_idx->bytes >= total * 4);
-        HIP_CHECK(hipMalloc(&d_offsets, n_rows * 8));
-        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                           n_rows, tile, d_bsums, d_offsets);
-        hipLaunchKernelGGL(k_probe_emit_bc64, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint64_t*)probe_keys->ptr, n_rows, t->log_bucket_size,
-                           t->first, t->next, t->build_keys64, mode, d_counts, d_offsets,
-                           (uint32_t*)out_probe_idx->ptr, (uint32_t*)out_build_idx->ptr);
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_offsets);
-    }
-    (void)hipFree(d_counts);
-    (void)hipFree(d_bsums);
-    return GPUE_OK;
+    return build_bucket_chained<uint64_t, HashU64>(s, keys, nullptr, row_count,
+                                                   gpue_join_table::BUCKET_CHAINED64,
+                                                   &gpue_join_table::build_keys64, out);
 }
 
 // ---------------------------------------------------------------------------
@@ -2149,7 +2164,8 @@ int gpue_join_build_linear_chained_u32(gpue_session* s, gpue_dbuf* keys, uint64_
                                        gpue_join_table** out) {
     ARG_CHECK(s && keys && out && row_count > 0 && row_count < LC_DATA_MASK);
     ARG_CHECK(keys->bytes >= (row_count + 1) * 4);
-    gpue_join_table* t = new gpue_join_table();
+    JoinTableOwner own(new gpue_join_table());
+    gpue_join_table* t = own.get();
     t->s = s;
     t->kind = gpue_join_table::LINEAR_CHAINED;
     t->row_count = row_count;
@@ -2167,7 +2183,7 @@ int gpue_join_build_linear_chained_u32(gpue_session* s, gpue_dbuf* keys, uint64_
                        s->stream, t->build_keys, row_count, t->log_bucket_size,
                        (uint32_t)(t->bucket_size - 1), t->first, t->next);
     HIP_CHECK(hipGetLastError());
-    *out = t;
+    *out = own.release();
     return GPUE_OK;
 }
 
@@ -2241,54 +2257,6 @@ __device__ static inline uint32_t dense_head(const int32_t* __restrict__ pk, uin
     return first[g.x + __popc(below)];
 }
 
-__global__ void k_probe_count_dense(const int32_t* __restrict__ probe_keys, uint64_t n,
-                                    int64_t mn, int64_t mx,
-                                    const uint2* __restrict__ groups,
-                                    const uint32_t* __restrict__ first,
-                                    const uint32_t* __restrict__ next, int mode,
-                                    uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t b = dense_head(probe_keys, i, mn, mx, groups, first);
-        uint32_t c = 0;
-        while (b != 0) { // chains hold identical keys: no compare
-            c++;
-            b = next[b];
-        }
-        row_counts[i] = join_mode_count(c, mode);
-    }
-}
-
-__global__ void k_probe_emit_dense(const int32_t* __restrict__ probe_keys, uint64_t n,
-                                   int64_t mn, int64_t mx,
-                                   const uint2* __restrict__ groups,
-                                   const uint32_t* __restrict__ first,
-                                   const uint32_t* __restrict__ next, int mode,
-                                   const uint32_t* __restrict__ row_counts,
-                                   const uint64_t* __restrict__ row_offsets,
-                                   uint32_t* __restrict__ out_probe,
-                                   uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (row_counts[i] == 0) continue;
-        uint64_t pos = row_offsets[i];
-        uint32_t b = dense_head(probe_keys, i, mn, mx, groups, first);
-        if (b == 0) { // unmatched emit (ANTI/OUTER)
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = 0;
-            continue;
-        }
-        if (mode == 2) continue;
-        while (b != 0) {
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = b;
-            pos++;
-            if (mode == 1) break;
-            b = next[b];
-        }
-    }
-}
-
 extern "C" int gpue_join_build_dense_range_direct_i32(gpue_session* s, gpue_dbuf* keys,
                                                       uint64_t row_count,
                                                       gpue_join_table** out);
@@ -2302,7 +2270,8 @@ int gpue_join_build_dense_range_direct_i32(gpue_session* s, gpue_dbuf* keys,
     uint64_t interval = (uint64_t)(mx - mn + 1);
     ARG_CHECK(interval < (1ull << 32));
     uint64_t ngroups = (interval + 31) / 32;
-    gpue_join_table* t = new gpue_join_table();
+    JoinTableOwner own(new gpue_join_table());
+    gpue_join_table* t = own.get();
     t->s = s;
     t->kind = gpue_join_table::DENSE_RANGE_DIRECT;
     t->min_key = mn;
@@ -2314,27 +2283,24 @@ int gpue_join_build_dense_range_direct_i32(gpue_session* s, gpue_dbuf* keys,
                        s->stream, (const int32_t*)keys->ptr, row_count, mn,
                        t->dense_groups);
     // start_index = exclusive scan of per-group popcounts (the loop at
-    // .hpp:878-881), via the block-sums scan used by the partition kernels
+    // .hpp:878-881)
+    DevScratch tmp;
+    CountScan scan;
     uint32_t* d_counts = nullptr;
-    uint64_t* d_bsums = nullptr;
     uint64_t* d_offsets = nullptr;
     uint32_t nb = grid_for(ngroups);
-    uint64_t tile = (ngroups + nb - 1) / nb;
-    HIP_CHECK(hipMalloc(&d_counts, ngroups * 4));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * 8));
-    HIP_CHECK(hipMalloc(&d_offsets, ngroups * 8));
+    HIP_CHECK(tmp.alloc(&d_counts, ngroups * 4));
+    HIP_CHECK(tmp.alloc(&d_offsets, ngroups * 8));
+    rc = scan.init(s, tmp, ngroups);
+    if (rc != GPUE_OK) return rc;
     hipLaunchKernelGGL(k_dense_popcounts, dim3(nb), dim3(BLOCK), 0, s->stream,
                        t->dense_groups, ngroups, d_counts);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                       ngroups, tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                       ngroups, tile, d_bsums, d_offsets);
+    uint64_t used = 0;
+    rc = scan.total(d_counts, &used);
+    if (rc != GPUE_OK) return rc;
+    scan.offsets(d_offsets);
     hipLaunchKernelGGL(k_dense_starts, dim3(nb), dim3(BLOCK), 0, s->stream,
                        t->dense_groups, ngroups, d_offsets);
-    uint64_t used = 0;
-    HIP_CHECK(hipMemcpyAsync(&used, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
     t->bucket_size = used; // number of present keys = first[] size
     HIP_CHECK(hipMalloc(&t->first, (used ? used : 1) * 4));
     HIP_CHECK(hipMalloc(&t->next, (row_count + 1) * 4));
@@ -2344,10 +2310,7 @@ int gpue_join_build_dense_range_direct_i32(gpue_session* s, gpue_dbuf* keys,
                        s->stream, (const int32_t*)keys->ptr, row_count, mn,
                        t->dense_groups, t->first, t->next);
     HIP_CHECK(hipGetLastError());
-    (void)hipFree(d_counts);
-    (void)hipFree(d_bsums);
-    (void)hipFree(d_offsets);
-    *out = t;
+    *out = own.release();
     return GPUE_OK;
 }
 
@@ -2467,287 +2430,6 @@ __device__ static inline uint32_t lc_lookup_head(uint32_t k, uint32_t log_bucket
     }
 }
 
-__global__ void k_probe_count_lc(const uint32_t* __restrict__ probe_keys, uint64_t n,
-                                 uint32_t log_bucket_size, uint32_t bucket_mask,
-                                 const uint32_t* __restrict__ first,
-                                 const uint32_t* __restrict__ next,
-                                 const uint32_t* __restrict__ build_keys, int mode,
-                                 uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t b = lc_lookup_head(probe_keys[i], log_bucket_size, bucket_mask, first,
-                                    build_keys);
-        uint32_t c = 0;
-        while (b != 0) {
-            c++;
-            b = next[b];
-        }
-        row_counts[i] = join_mode_count(c, mode);
-    }
-}
-
-__global__ void k_probe_emit_lc(const uint32_t* __restrict__ probe_keys, uint64_t n,
-                                uint32_t log_bucket_size, uint32_t bucket_mask,
-                                const uint32_t* __restrict__ first,
-                                const uint32_t* __restrict__ next,
-                                const uint32_t* __restrict__ build_keys, int mode,
-                                const uint32_t* __restrict__ row_counts,
-                                const uint64_t* __restrict__ row_offsets,
-                                uint32_t* __restrict__ out_probe,
-                                uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (row_counts[i] == 0) continue;
-        uint64_t pos = row_offsets[i];
-        uint32_t b = lc_lookup_head(probe_keys[i], log_bucket_size, bucket_mask, first,
-                                    build_keys);
-        if (b == 0) { // unmatched emit (ANTI/OUTER)
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = 0;
-            continue;
-        }
-        if (mode == 2) continue;
-        while (b != 0) {
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = b;
-            pos++;
-            if (mode == 1) break;
-            b = next[b];
-        }
-    }
-}
-
-// probe with key-equality compare along the chain (lookup_init +
-// _probe_from_ht with AreKeysInChainIdentical == false)
-__global__ void k_probe_count_bc(const uint32_t* __restrict__ probe_keys, uint64_t n,
-                                 uint32_t log_bucket_size, const uint32_t* __restrict__ first,
-                                 const uint32_t* __restrict__ next,
-                                 const uint32_t* __restrict__ build_keys, int mode,
-                                 uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t k = probe_keys[i];
-        uint32_t b = first[join_hash_u32(k, log_bucket_size)];
-        uint32_t c = 0;
-        while (b != 0) {
-            c += (build_keys[b] == k);
-            b = next[b];
-        }
-        row_counts[i] = join_mode_count(c, mode);
-    }
-}
-
-__global__ void k_probe_emit_bc(const uint32_t* __restrict__ probe_keys, uint64_t n,
-                                uint32_t log_bucket_size, const uint32_t* __restrict__ first,
-                                const uint32_t* __restrict__ next,
-                                const uint32_t* __restrict__ build_keys, int mode,
-                                const uint32_t* __restrict__ row_counts,
-                                const uint64_t* __restrict__ row_offsets,
-                                uint32_t* __restrict__ out_probe,
-                                uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (row_counts[i] == 0) continue;
-        uint32_t k = probe_keys[i];
-        uint64_t pos = row_offsets[i];
-        uint32_t b = first[join_hash_u32(k, log_bucket_size)];
-        bool any = false;
-        while (b != 0) {
-            if (build_keys[b] == k) {
-                any = true;
-                if (mode != 2) {
-                    out_probe[pos] = (uint32_t)i;
-                    out_build[pos] = b;
-                    pos++;
-                }
-                if (mode == 1 || mode == 2) break;
-            }
-            b = next[b];
-        }
-        if (!any && (mode == 2 || mode == 3)) {
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = 0;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------
-// hash-join probe: lookup + chain-walk emit (reference
-// join_hash_map_method.hpp:688-707 lookup_init + join_hash_map.hpp:717-795
-// _probe_from_ht). Two-phase count/emit replaces the CPU's resumable cursor
-// (SURVEY.md §7 hard part (c)); output ordered by probe row.
-// ---------------------------------------------------------------------------
-// block-wise scan for row offsets: pass A block sums, host scan, pass B add
-__global__ void k_block_sums_u32(const uint32_t* __restrict__ v, uint64_t n, uint64_t tile,
-                                 uint64_t* __restrict__ sums) {
-    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
-    uint64_t c = 0;
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) c += v[i];
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-        c += __shfl_down((unsigned long long)c, off, WAVE);
-    __shared__ uint64_t wsum[BLOCK / WAVE];
-    int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
-    if (lane == 0) wsum[wid] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t t = 0;
-        for (int w = 0; w < BLOCK / WAVE; w++) t += wsum[w];
-        sums[blockIdx.x] = t;
-    }
-}
-
-// Range-direct chains hold IDENTICAL keys by construction
-// (AreKeysInChainIdentical, join_hash_map_method.h:264), so the probe needs
-// no build-key compare: count = chain length. The public entry re-walks with
-// that simplification.
-__global__ void k_probe_count_rd(const int32_t* __restrict__ probe_keys, uint64_t n,
-                                 int64_t mn, int64_t mx, const uint32_t* __restrict__ first,
-                                 const uint32_t* __restrict__ next, int mode,
-                                 uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        int32_t k = probe_keys[i];
-        uint32_t c = 0;
-        if (k >= mn && k <= mx) {
-            uint32_t b = first[k - mn];
-            while (b != 0) {
-                c++;
-                b = next[b];
-            }
-        }
-        row_counts[i] = join_mode_count(c, mode);
-    }
-}
-
-__global__ void k_probe_emit_rd(const int32_t* __restrict__ probe_keys, uint64_t n,
-                                int64_t mn, int64_t mx, const uint32_t* __restrict__ first,
-                                const uint32_t* __restrict__ next, int mode,
-                                const uint32_t* __restrict__ row_counts,
-                                const uint64_t* __restrict__ row_offsets,
-                                uint32_t* __restrict__ out_probe,
-                                uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (row_counts[i] == 0) continue;
-        uint64_t pos = row_offsets[i];
-        int32_t k = probe_keys[i];
-        uint32_t b = (k >= mn && k <= mx) ? first[k - mn] : 0;
-        if (b == 0) { // only reachable for ANTI/OUTER: the unmatched emit
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = 0;
-            continue;
-        }
-        if (mode == 2) continue; // matched row contributes nothing to ANTI
-        while (b != 0) {
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = b;
-            pos++;
-            if (mode == 1) break; // SEMI: first match only
-            b = next[b];
-        }
-    }
-}
-
-// exclusive scan of u32 counts into u64 offsets — block sums + thread0 scan +
-// per-block add; test-path sizes (≤ tens of M rows), not the bench hot loop
-__global__ void k_scan_offsets(const uint32_t* __restrict__ counts, uint64_t n, uint64_t tile,
-                               const uint64_t* __restrict__ block_offsets,
-                               uint64_t* __restrict__ offsets) {
-    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
-    if (threadIdx.x == 0) {
-        uint64_t acc = block_offsets[blockIdx.x];
-        for (uint64_t i = lo; i < hi; i++) {
-            offsets[i] = acc;
-            acc += counts[i];
-        }
-    }
-}
-
-extern "C" int gpue_join_probe_emit_mode_i32(gpue_session* s, gpue_join_table* t,
-                                             gpue_dbuf* probe_keys, uint64_t n_rows, int mode,
-                                             gpue_dbuf* out_probe_idx,
-                                             gpue_dbuf* out_build_idx, uint64_t* match_count);
-
-int gpue_join_probe_emit_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
-                             uint64_t n_rows, gpue_dbuf* out_probe_idx,
-                             gpue_dbuf* out_build_idx, uint64_t* match_count) {
-    return gpue_join_probe_emit_mode_i32(s, t, probe_keys, n_rows, 0, out_probe_idx,
-                                         out_build_idx, match_count);
-}
-
-int gpue_join_probe_emit_mode_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
-                                  uint64_t n_rows, int mode, gpue_dbuf* out_probe_idx,
-                                  gpue_dbuf* out_build_idx, uint64_t* match_count) {
-    ARG_CHECK(s && t && probe_keys && match_count && t->next != nullptr);
-    ARG_CHECK(mode >= 0 && mode <= 3);
-    ARG_CHECK(probe_keys->bytes >= n_rows * 4);
-    uint32_t nb = grid_for(n_rows);
-    uint64_t tile = (n_rows + nb - 1) / nb;
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bsums = nullptr;
-    uint64_t* d_offsets = nullptr;
-    HIP_CHECK(hipMalloc(&d_counts, n_rows * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * sizeof(uint64_t)));
-    if (t->kind == gpue_join_table::LINEAR_CHAINED) {
-        hipLaunchKernelGGL(k_probe_count_lc, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)probe_keys->ptr, n_rows, t->log_bucket_size,
-                           (uint32_t)(t->bucket_size - 1), t->first, t->next, t->build_keys,
-                           mode, d_counts);
-    } else if (t->kind == gpue_join_table::BUCKET_CHAINED) {
-        hipLaunchKernelGGL(k_probe_count_bc, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)probe_keys->ptr, n_rows, t->log_bucket_size,
-                           t->first, t->next, t->build_keys, mode, d_counts);
-    } else if (t->kind == gpue_join_table::DENSE_RANGE_DIRECT) {
-        hipLaunchKernelGGL(k_probe_count_dense, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const int32_t*)probe_keys->ptr, n_rows, t->min_key, t->max_key,
-                           t->dense_groups, t->first, t->next, mode, d_counts);
-    } else
-    hipLaunchKernelGGL(k_probe_count_rd, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const int32_t*)probe_keys->ptr, n_rows, t->min_key, t->max_key,
-                       t->first, t->next, mode, d_counts);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       d_counts, n_rows, tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, sizeof(uint64_t), hipMemcpyDeviceToHost,
-                             s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    *match_count = total;
-    if (out_probe_idx && out_build_idx && total > 0) {
-        ARG_CHECK(out_probe_idx->bytes >= total * 4 && out_build_idx->bytes >= total * 4);
-        HIP_CHECK(hipMalloc(&d_offsets, n_rows * sizeof(uint64_t)));
-        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           d_counts, n_rows, tile, d_bsums, d_offsets);
-        if (t->kind == gpue_join_table::LINEAR_CHAINED) {
-            hipLaunchKernelGGL(k_probe_emit_lc, dim3(nb), dim3(BLOCK), 0, s->stream,
-                               (const uint32_t*)probe_keys->ptr, n_rows, t->log_bucket_size,
-                               (uint32_t)(t->bucket_size - 1), t->first, t->next,
-                               t->build_keys, mode, d_counts, d_offsets,
-                               (uint32_t*)out_probe_idx->ptr, (uint32_t*)out_build_idx->ptr);
-        } else if (t->kind == gpue_join_table::BUCKET_CHAINED) {
-            hipLaunchKernelGGL(k_probe_emit_bc, dim3(nb), dim3(BLOCK), 0, s->stream,
-                               (const uint32_t*)probe_keys->ptr, n_rows, t->log_bucket_size,
-                               t->first, t->next, t->build_keys, mode, d_counts, d_offsets,
-                               (uint32_t*)out_probe_idx->ptr, (uint32_t*)out_build_idx->ptr);
-        } else if (t->kind == gpue_join_table::DENSE_RANGE_DIRECT) {
-            hipLaunchKernelGGL(k_probe_emit_dense, dim3(nb), dim3(BLOCK), 0, s->stream,
-                               (const int32_t*)probe_keys->ptr, n_rows, t->min_key,
-                               t->max_key, t->dense_groups, t->first, t->next, mode,
-                               d_counts, d_offsets, (uint32_t*)out_probe_idx->ptr,
-                               (uint32_t*)out_build_idx->ptr);
-        } else
-        hipLaunchKernelGGL(k_probe_emit_rd, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const int32_t*)probe_keys->ptr, n_rows, t->min_key, t->max_key,
-                           t->first, t->next, mode, d_counts, d_offsets,
-                           (uint32_t*)out_probe_idx->ptr, (uint32_t*)out_build_idx->ptr);
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_offsets);
-    }
-    (void)hipFree(d_counts);
-    (void)hipFree(d_bsums);
-    return GPUE_OK;
-}
-
 // ---------------------------------------------------------------------------
 // Dictionary-encoded binary page decode (binary_dict_page.cpp:229-280): the
 // data page's int32 codewords (bitshuffle layer handled by
@@ -2793,37 +2475,31 @@ int gpue_dict_decode_binary(gpue_session* s, gpue_dbuf* dict_bytes, gpue_dbuf* d
                             gpue_dbuf* out_offsets, uint64_t* total_bytes) {
     ARG_CHECK(s && dict_bytes && dict_offsets && codes && total_bytes);
     ARG_CHECK(codes->bytes >= n * 4);
+    DevScratch tmp;
+    CountScan scan;
     uint32_t nb = grid_for(n);
-    uint64_t tile = (n + nb - 1) / nb;
     uint32_t* d_lens = nullptr;
-    uint64_t* d_bsums = nullptr;
     uint64_t* d_off = nullptr;
-    HIP_CHECK(hipMalloc(&d_lens, n * 4));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * 8));
+    HIP_CHECK(tmp.alloc(&d_lens, n * 4));
+    int rc = scan.init(s, tmp, n);
+    if (rc != GPUE_OK) return rc;
     hipLaunchKernelGGL(k_dict_code_lengths, dim3(nb), dim3(BLOCK), 0, s->stream,
                        (const int32_t*)codes->ptr, n, (const uint32_t*)dict_offsets->ptr,
                        d_lens);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_lens, n,
-                       tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
     uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
+    rc = scan.total(d_lens, &total);
+    if (rc != GPUE_OK) return rc;
     *total_bytes = total;
     if (out_bytes && out_offsets) {
         ARG_CHECK(out_bytes->bytes >= total && out_offsets->bytes >= (n + 1) * 4);
-        HIP_CHECK(hipMalloc(&d_off, n * 8));
-        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_lens, n,
-                           tile, d_bsums, d_off);
+        HIP_CHECK(tmp.alloc(&d_off, n * 8));
+        scan.offsets(d_off);
         hipLaunchKernelGGL(k_dict_emit, dim3(nb), dim3(BLOCK), 0, s->stream,
                            (const int32_t*)codes->ptr, n, (const uint8_t*)dict_bytes->ptr,
                            (const uint32_t*)dict_offsets->ptr, d_off, total,
                            (uint8_t*)out_bytes->ptr, (uint32_t*)out_offsets->ptr);
         HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_off);
     }
-    (void)hipFree(d_lens);
-    (void)hipFree(d_bsums);
     return GPUE_OK;
 }
 
@@ -3653,74 +3329,6 @@ __device__ static inline bool slice_eq(const uint8_t* a, uint32_t alen, const ui
     return true;
 }
 
-__global__ void k_probe_count_vc(const uint8_t* __restrict__ pbytes,
-                                 const uint32_t* __restrict__ poffsets, uint64_t n,
-                                 uint32_t bucket_mask, const uint32_t* __restrict__ first,
-                                 const uint32_t* __restrict__ next,
-                                 const uint8_t* __restrict__ bbytes,
-                                 const uint32_t* __restrict__ boffsets,
-                                 const uint8_t* __restrict__ pnulls /*may be null*/,
-                                 int mode, uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (mode == 6 && pnulls && pnulls[i]) {
-            // NULL_AWARE_LEFT_ANTI (NOT IN): null probe rows excluded
-            // (join_hash_map.hpp:1225-1240)
-            row_counts[i] = 0;
-            continue;
-        }
-        uint32_t len = poffsets[i + 1] - poffsets[i];
-        uint32_t b = crc_hash_32_dev(pbytes + poffsets[i], len, 0x811C9DC5u) & bucket_mask;
-        uint32_t j = (pnulls && pnulls[i]) ? 0u : first[b];
-        uint32_t c = 0;
-        while (j != 0) {
-            c += slice_eq(bbytes + boffsets[j], boffsets[j + 1] - boffsets[j],
-                          pbytes + poffsets[i], len);
-            j = next[j];
-        }
-        row_counts[i] = join_mode_count(c, mode == 6 ? 2 : mode);
-    }
-}
-
-__global__ void k_probe_emit_vc(const uint8_t* __restrict__ pbytes,
-                                const uint32_t* __restrict__ poffsets, uint64_t n,
-                                uint32_t bucket_mask, const uint32_t* __restrict__ first,
-                                const uint32_t* __restrict__ next,
-                                const uint8_t* __restrict__ bbytes,
-                                const uint32_t* __restrict__ boffsets,
-                                const uint8_t* __restrict__ pnulls /*may be null*/,
-                                int mode, const uint32_t* __restrict__ row_counts,
-                                const uint64_t* __restrict__ row_offsets,
-                                uint32_t* __restrict__ out_probe,
-                                uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (row_counts[i] == 0) continue;
-        uint64_t pos = row_offsets[i];
-        uint32_t len = poffsets[i + 1] - poffsets[i];
-        uint32_t b = crc_hash_32_dev(pbytes + poffsets[i], len, 0x811C9DC5u) & bucket_mask;
-        uint32_t j = (pnulls && pnulls[i]) ? 0u : first[b];
-        uint32_t c = 0;
-        while (j != 0) {
-            if (slice_eq(bbytes + boffsets[j], boffsets[j + 1] - boffsets[j],
-                         pbytes + poffsets[i], len)) {
-                if (mode == 0 || mode == 3 || (mode == 1 && c == 0)) {
-                    out_probe[pos] = (uint32_t)i;
-                    out_build[pos] = j;
-                    pos++;
-                }
-                c++;
-                if (mode == 1 || mode == 2) break;
-            }
-            j = next[j];
-        }
-        if (c == 0 && (mode == 2 || mode == 3)) { // unmatched emit, build 0 = NULL
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = 0;
-        }
-    }
-}
-
 extern "C" {
 int gpue_join_build_varchar(gpue_session* s, gpue_dbuf* bytes, gpue_dbuf* offsets,
                             uint64_t row_count, gpue_join_table** out);
@@ -3751,7 +3359,8 @@ int gpue_join_build_varchar_nulls(gpue_session* s, gpue_dbuf* bytes, gpue_dbuf* 
                                   gpue_join_table** out) {
     ARG_CHECK(s && bytes && offsets && out && row_count > 0);
     ARG_CHECK(offsets->bytes >= (row_count + 2) * 4);
-    gpue_join_table* t = new gpue_join_table();
+    JoinTableOwner own(new gpue_join_table());
+    gpue_join_table* t = own.get();
     t->s = s;
     t->kind = gpue_join_table::VARCHAR;
     t->row_count = row_count;
@@ -3777,7 +3386,7 @@ int gpue_join_build_varchar_nulls(gpue_session* s, gpue_dbuf* bytes, gpue_dbuf* 
                        t->key_bytes, t->key_offsets, t->key_nulls, row_count,
                        (uint32_t)(t->bucket_size - 1), t->first, t->next);
     HIP_CHECK(hipGetLastError());
-    *out = t;
+    *out = own.release();
     return GPUE_OK;
 }
 
@@ -3797,54 +3406,6 @@ int gpue_join_probe_emit_varchar_mode(gpue_session* s, gpue_join_table* t, gpue_
                                               out_probe_idx, out_build_idx, match_count);
 }
 
-int gpue_join_probe_emit_varchar_nulls(gpue_session* s, gpue_join_table* t, gpue_dbuf* pbytes,
-                                       gpue_dbuf* poffsets, gpue_dbuf* pnulls,
-                                       uint64_t n_rows, int mode, gpue_dbuf* out_probe_idx,
-                                       gpue_dbuf* out_build_idx, uint64_t* match_count) {
-    ARG_CHECK(s && t && pbytes && poffsets && match_count);
-    ARG_CHECK((mode >= 0 && mode <= 3) || mode == 6);
-    ARG_CHECK(t->kind == gpue_join_table::VARCHAR);
-    ARG_CHECK(poffsets->bytes >= (n_rows + 1) * 4);
-    uint32_t nb = grid_for(n_rows);
-    uint64_t tile = (n_rows + nb - 1) / nb;
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bsums = nullptr;
-    uint64_t* d_offsets = nullptr;
-    HIP_CHECK(hipMalloc(&d_counts, n_rows * 4));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * 8));
-    hipLaunchKernelGGL(k_probe_count_vc, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint8_t*)pbytes->ptr, (const uint32_t*)poffsets->ptr, n_rows,
-                       (uint32_t)(t->bucket_size - 1), t->first, t->next, t->key_bytes,
-                       t->key_offsets, pnulls ? (const uint8_t*)pnulls->ptr : nullptr,
-                       mode, d_counts);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                       n_rows, tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    *match_count = total;
-    if (out_probe_idx && out_build_idx && total > 0) {
-        ARG_CHECK(out_probe_idx->bytes >= total * 4 && out_build_idx->bytes >= total * 4);
-        HIP_CHECK(hipMalloc(&d_offsets, n_rows * 8));
-        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                           n_rows, tile, d_bsums, d_offsets);
-        hipLaunchKernelGGL(k_probe_emit_vc, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint8_t*)pbytes->ptr, (const uint32_t*)poffsets->ptr,
-                           n_rows, (uint32_t)(t->bucket_size - 1), t->first, t->next,
-                           t->key_bytes, t->key_offsets,
-                           pnulls ? (const uint8_t*)pnulls->ptr : nullptr,
-                           mode == 6 ? 2 : mode, d_counts,
-                           d_offsets, (uint32_t*)out_probe_idx->ptr,
-                           (uint32_t*)out_build_idx->ptr);
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_offsets);
-    }
-    (void)hipFree(d_counts);
-    (void)hipFree(d_bsums);
-    return GPUE_OK;
-}
-
 // ---------------------------------------------------------------------------
 // 16-byte (LARGEINT / SERIALIZED_FIXED_SIZE_LARGEINT) bucket-chained join —
 // the generic JoinKeyHash<T,16> path: crc_hash_32 over the 16 key bytes,
@@ -3852,73 +3413,6 @@ int gpue_join_probe_emit_varchar_nulls(gpue_session* s, gpue_join_table* t, gpue
 // Functionally equal to the varchar path with fixed 16-byte slices (the
 // oracle pin reuses exactly that), minus the per-row offsets indirection.
 // ---------------------------------------------------------------------------
-__global__ void k_build_bucket_chained128(const ulonglong2* __restrict__ keys,
-                                          uint64_t row_count, uint32_t bucket_mask,
-                                          uint32_t* __restrict__ first,
-                                          uint32_t* __restrict__ next) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = 1 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= row_count;
-         i += stride) {
-        ulonglong2 k = keys[i];
-        uint32_t b = crc_hash_32_dev((const uint8_t*)&k, 16, 0x811C9DC5u) & bucket_mask;
-        next[i] = atomicExch(&first[b], (uint32_t)i);
-    }
-}
-
-__global__ void k_probe_count_u128(const ulonglong2* __restrict__ probe_keys, uint64_t n,
-                                   uint32_t bucket_mask, const uint32_t* __restrict__ first,
-                                   const uint32_t* __restrict__ next,
-                                   const ulonglong2* __restrict__ build_keys, int mode,
-                                   uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        ulonglong2 k = probe_keys[i];
-        uint32_t b = first[crc_hash_32_dev((const uint8_t*)&k, 16, 0x811C9DC5u) & bucket_mask];
-        uint32_t c = 0;
-        while (b != 0) {
-            ulonglong2 bk = build_keys[b];
-            c += (bk.x == k.x) & (bk.y == k.y);
-            b = next[b];
-        }
-        row_counts[i] = join_mode_count(c, mode);
-    }
-}
-
-__global__ void k_probe_emit_u128(const ulonglong2* __restrict__ probe_keys, uint64_t n,
-                                  uint32_t bucket_mask, const uint32_t* __restrict__ first,
-                                  const uint32_t* __restrict__ next,
-                                  const ulonglong2* __restrict__ build_keys, int mode,
-                                  const uint32_t* __restrict__ row_counts,
-                                  const uint64_t* __restrict__ row_offsets,
-                                  uint32_t* __restrict__ out_probe,
-                                  uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (row_counts[i] == 0) continue;
-        uint64_t pos = row_offsets[i];
-        ulonglong2 k = probe_keys[i];
-        uint32_t b = first[crc_hash_32_dev((const uint8_t*)&k, 16, 0x811C9DC5u) & bucket_mask];
-        bool any = false;
-        while (b != 0) {
-            ulonglong2 bk = build_keys[b];
-            if ((bk.x == k.x) & (bk.y == k.y)) {
-                any = true;
-                if (mode != 2) {
-                    out_probe[pos] = (uint32_t)i;
-                    out_build[pos] = b;
-                    pos++;
-                }
-                if (mode == 1 || mode == 2) break;
-            }
-            b = next[b];
-        }
-        if (!any && (mode == 2 || mode == 3)) {
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = 0;
-        }
-    }
-}
-
 extern "C" {
 int gpue_join_build_bucket_chained_u128(gpue_session* s, gpue_dbuf* keys /*16 B, 1-based*/,
                                         uint64_t row_count, gpue_join_table** out);
@@ -3928,30 +3422,383 @@ int gpue_join_probe_emit_mode_u128(gpue_session* s, gpue_join_table* t,
                                    uint64_t* match_count);
 }
 
+struct HashU128 {
+    uint32_t bucket_mask;
+    static HashU128 of(const gpue_join_table* t) { return {(uint32_t)(t->bucket_size - 1)}; }
+    __device__ uint32_t operator()(const ulonglong2& k) const {
+        return crc_hash_32_dev((const uint8_t*)&k, 16, 0x811C9DC5u) & bucket_mask;
+    }
+};
+
 int gpue_join_build_bucket_chained_u128(gpue_session* s, gpue_dbuf* keys,
                                         uint64_t row_count, gpue_join_table** out) {
     ARG_CHECK(s && keys && out && row_count > 0 && row_count + 1 < (1ull << 31));
     ARG_CHECK(keys->bytes >= (row_count + 1) * 16);
-    gpue_join_table* t = new gpue_join_table();
-    t->s = s;
-    t->kind = gpue_join_table::BUCKET_CHAINED128;
-    t->row_count = row_count;
-    t->bucket_size = calc_bucket_size((uint32_t)(row_count + 1));
-    t->log_bucket_size = (uint32_t)__builtin_ctzll(t->bucket_size);
-    HIP_CHECK(hipMalloc(&t->first, t->bucket_size * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&t->next, (row_count + 1) * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&t->build_keys128, (row_count + 1) * sizeof(ulonglong2)));
-    HIP_CHECK(hipMemsetAsync(t->first, 0, t->bucket_size * sizeof(uint32_t), s->stream));
-    HIP_CHECK(hipMemsetAsync(t->next, 0, (row_count + 1) * sizeof(uint32_t), s->stream));
-    HIP_CHECK(hipMemcpyAsync(t->build_keys128, keys->ptr,
-                             (row_count + 1) * sizeof(ulonglong2),
-                             hipMemcpyDeviceToDevice, s->stream));
-    hipLaunchKernelGGL(k_build_bucket_chained128, dim3(grid_for(row_count)), dim3(BLOCK), 0,
-                       s->stream, t->build_keys128, row_count,
-                       (uint32_t)(t->bucket_size - 1), t->first, t->next);
-    HIP_CHECK(hipGetLastError());
-    *out = t;
+    return build_bucket_chained<ulonglong2, HashU128>(s, keys, nullptr, row_count,
+                                                      gpue_join_table::BUCKET_CHAINED128,
+                                                      &gpue_join_table::build_keys128, out);
+}
+
+// ---------------------------------------------------------------------------
+// Generic hash-join probe: lookup + chain-walk emit (reference
+// join_hash_map_method.hpp:688-707 lookup_init + join_hash_map.hpp:717-795
+// _probe_from_ht). Two-phase count/emit replaces the CPU's resumable cursor
+// (SURVEY.md §7 hard part (c)); output ordered by probe row, chain order
+// within a probe row.
+//
+// One kernel trio (count, emit, right-mark) over a LOOKUP POLICY per table
+// shape, passed by value. A policy holds the table and probe pointers and says
+//   is_null(i)   whether probe row i is null (matches nothing)
+//   load(i)      probe row i's key
+//   head(i, k)   the chain head for it: 0 = no chain / out of range
+//   match(b, k)  whether chain entry b holds k — only asked when COMPARE;
+//                range-direct, dense and linear chains hold IDENTICAL keys
+//                (AreKeysInChainIdentical, join_hash_map_method.h:264)
+//   next         the chain links
+// A new key shape supplies a policy and an entry point; nothing else.
+// ---------------------------------------------------------------------------
+struct ProbeRangeDirect {
+    static constexpr bool COMPARE = false;
+    using Key = int32_t;
+    const int32_t* __restrict__ probe_keys;
+    int64_t mn, mx;
+    const uint32_t* __restrict__ first;
+    const uint32_t* __restrict__ next;
+    __device__ bool is_null(uint64_t) const { return false; }
+    __device__ Key load(uint64_t i) const { return probe_keys[i]; }
+    __device__ uint32_t head(uint64_t, Key k) const {
+        return (k >= mn && k <= mx) ? first[k - mn] : 0;
+    }
+    __device__ bool match(uint32_t, Key) const { return true; }
+};
+
+struct ProbeDense { // rank/select head (dense_head reads the key itself)
+    static constexpr bool COMPARE = false;
+    using Key = int32_t;
+    const int32_t* __restrict__ probe_keys;
+    int64_t mn, mx;
+    const uint2* __restrict__ groups;
+    const uint32_t* __restrict__ first;
+    const uint32_t* __restrict__ next;
+    __device__ bool is_null(uint64_t) const { return false; }
+    __device__ Key load(uint64_t) const { return 0; }
+    __device__ uint32_t head(uint64_t i, Key) const {
+        return dense_head(probe_keys, i, mn, mx, groups, first);
+    }
+    __device__ bool match(uint32_t, Key) const { return true; }
+};
+
+struct ProbeLinear { // the fingerprint + key search ends at the key's own chain
+    static constexpr bool COMPARE = false;
+    using Key = uint32_t;
+    const uint32_t* __restrict__ probe_keys;
+    uint32_t log_bucket_size, bucket_mask;
+    const uint32_t* __restrict__ first;
+    const uint32_t* __restrict__ next;
+    const uint32_t* __restrict__ build_keys;
+    __device__ bool is_null(uint64_t) const { return false; }
+    __device__ Key load(uint64_t i) const { return probe_keys[i]; }
+    __device__ uint32_t head(uint64_t, Key k) const {
+        return lc_lookup_head(k, log_bucket_size, bucket_mask, first, build_keys);
+    }
+    __device__ bool match(uint32_t, Key) const { return true; }
+};
+
+__device__ static inline bool key_eq(uint32_t a, uint32_t b) { return a == b; }
+__device__ static inline bool key_eq(uint64_t a, uint64_t b) { return a == b; }
+__device__ static inline bool key_eq(const ulonglong2& a, const ulonglong2& b) {
+    return (a.x == b.x) & (a.y == b.y);
+}
+
+// bucket-chained, any fixed key width: buckets are shared, so the walk
+// compares (_probe_from_ht with AreKeysInChainIdentical == false). Keys go
+// by reference: the 16-byte crc reads the loaded key's bytes in place
+template <class K, class H>
+struct ProbeChained {
+    static constexpr bool COMPARE = true;
+    using Key = K;
+    const K* __restrict__ probe_keys;
+    H hash;
+    const uint32_t* __restrict__ first;
+    const uint32_t* __restrict__ next;
+    const K* __restrict__ build_keys;
+    __device__ bool is_null(uint64_t) const { return false; }
+    __device__ Key load(uint64_t i) const { return probe_keys[i]; }
+    __device__ uint32_t head(uint64_t, const Key& k) const { return first[hash(k)]; }
+    __device__ bool match(uint32_t b, const Key& k) const {
+        return key_eq(build_keys[b], k);
+    }
+};
+
+struct ProbeVarchar { // Slice keys: crc hash, byte compare
+    static constexpr bool COMPARE = true;
+    struct Key {
+        const uint8_t* p;
+        uint32_t len;
+    };
+    const uint8_t* __restrict__ pbytes;
+    const uint32_t* __restrict__ poffsets;
+    uint32_t bucket_mask;
+    const uint32_t* __restrict__ first;
+    const uint32_t* __restrict__ next;
+    const uint8_t* __restrict__ bbytes;
+    const uint32_t* __restrict__ boffsets;
+    __device__ bool is_null(uint64_t) const { return false; }
+    __device__ Key load(uint64_t i) const {
+        return {pbytes + poffsets[i], poffsets[i + 1] - poffsets[i]};
+    }
+    __device__ uint32_t head(uint64_t, Key k) const {
+        return first[crc_hash_32_dev(k.p, k.len, 0x811C9DC5u) & bucket_mask];
+    }
+    __device__ bool match(uint32_t b, Key k) const {
+        return slice_eq(bbytes + boffsets[b], boffsets[b + 1] - boffsets[b], k.p, k.len);
+    }
+};
+
+// Nullable probe column over any shape (lookup_init is_nulls path): a null
+// probe key matches nothing — INNER/SEMI emit nothing for it, ANTI/OUTER emit
+// the unmatched (i, 0) row.
+template <class P>
+struct WithNulls : P {
+    const uint8_t* __restrict__ nulls;
+    __device__ bool is_null(uint64_t i) const { return nulls[i] != 0; }
+};
+
+template <class P>
+__global__ void k_probe_count(P p, uint64_t n, int mode, int skip_nulls,
+                              uint32_t* __restrict__ row_counts) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint32_t c = 0;
+        if (p.is_null(i)) {
+            if (skip_nulls) {
+                row_counts[i] = 0;
+                continue;
+            }
+        } else {
+            typename P::Key k = p.load(i);
+            for (uint32_t b = p.head(i, k); b != 0; b = p.next[b])
+                c += P::COMPARE ? (uint32_t)p.match(b, k) : 1u;
+        }
+        row_counts[i] = join_mode_count(c, mode);
+    }
+}
+
+// all LEFT modes: walk the chain; a match emits (i, b) unless ANTI; SEMI and
+// ANTI stop at the first match; nothing matched emits (i, 0) for ANTI/OUTER
+template <class P>
+__global__ void k_probe_emit(P p, uint64_t n, int mode,
+                             const uint32_t* __restrict__ row_counts,
+                             const uint64_t* __restrict__ row_offsets,
+                             uint32_t* __restrict__ out_probe,
+                             uint32_t* __restrict__ out_build) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (row_counts[i] == 0) continue;
+        uint64_t pos = row_offsets[i];
+        // matches seen. Identical-key chains match iff they exist, known before
+        // the walk; compared chains count (a bool there costs per-step mask upkeep)
+        uint32_t c = 0;
+        if (!p.is_null(i)) {
+            typename P::Key k = p.load(i);
+            uint32_t b = p.head(i, k);
+            if (!P::COMPARE) c = b != 0;
+            for (; b != 0; b = p.next[b]) {
+                if (P::COMPARE) {
+                    if (!p.match(b, k)) continue;
+                    c++;
+                }
+                if (mode != GPUE_JOIN_LEFT_ANTI) {
+                    out_probe[pos] = (uint32_t)i;
+                    out_build[pos] = b;
+                    pos++;
+                }
+                if (mode == GPUE_JOIN_LEFT_SEMI || mode == GPUE_JOIN_LEFT_ANTI) break;
+            }
+        }
+        if (c == 0 && (mode == GPUE_JOIN_LEFT_ANTI || mode == GPUE_JOIN_LEFT_OUTER)) {
+            out_probe[pos] = (uint32_t)i; // unmatched: build 0 = NULL
+            out_build[pos] = 0;
+        }
+    }
+}
+
+// RIGHT SEMI/ANTI (join_hash_map.hpp _probe_from_ht_for_right_*): the probe
+// pass marks matched BUILD rows; output = matched (semi) / unmatched (anti)
+// build rows, compacted in build-row order.
+template <class P>
+__global__ void k_right_mark(P p, uint64_t n, uint32_t* __restrict__ matched_bits) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (p.is_null(i)) continue;
+        typename P::Key k = p.load(i);
+        for (uint32_t b = p.head(i, k); b != 0; b = p.next[b])
+            if (!P::COMPARE || p.match(b, k)) atomicOr(&matched_bits[b >> 5], 1u << (b & 31));
+    }
+}
+
+__global__ void k_right_row_counts(const uint32_t* __restrict__ matched_bits,
+                                   uint64_t build_rows, int anti,
+                                   uint32_t* __restrict__ row_counts) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < build_rows;
+         j += stride) {
+        uint32_t b = (uint32_t)j + 1; // build rows are 1-based
+        uint32_t m = (matched_bits[b >> 5] >> (b & 31)) & 1u;
+        row_counts[j] = anti ? (1u - m) : m;
+    }
+}
+
+__global__ void k_right_emit(const uint32_t* __restrict__ row_counts,
+                             const uint64_t* __restrict__ row_offsets, uint64_t build_rows,
+                             uint32_t* __restrict__ out_build) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < build_rows;
+         j += stride)
+        if (row_counts[j]) out_build[row_offsets[j]] = (uint32_t)j + 1;
+}
+
+template <class P>
+static int probe_emit(gpue_session* s, const P& p, uint64_t n_rows, int mode,
+                      gpue_dbuf* out_probe_idx, gpue_dbuf* out_build_idx,
+                      uint64_t* match_count) {
+    // NULL_AWARE_LEFT_ANTI (mode 6, the NOT IN lowering,
+    // join_hash_map.hpp:1225-1240) is LEFT_ANTI with null probe rows EXCLUDED
+    // — NULL NOT IN (...) is never true — where plain LEFT_ANTI emits them as
+    // unmatched. Lowered here, once, for every shape: null rows count 0.
+    const int skip_nulls = mode == 6;
+    if (skip_nulls) mode = GPUE_JOIN_LEFT_ANTI;
+    return probe_count_scan_emit(
+        s, n_rows, out_probe_idx, out_build_idx, match_count,
+        [&](uint32_t nb, uint32_t* d_counts) {
+            hipLaunchKernelGGL((k_probe_count<P>), dim3(nb), dim3(BLOCK), 0, s->stream, p,
+                               n_rows, mode, skip_nulls, d_counts);
+        },
+        [&](uint32_t nb, const uint32_t* d_counts, const uint64_t* d_offsets,
+            uint32_t* out_probe, uint32_t* out_build) {
+            hipLaunchKernelGGL((k_probe_emit<P>), dim3(nb), dim3(BLOCK), 0, s->stream, p,
+                               n_rows, mode, d_counts, d_offsets, out_probe, out_build);
+        });
+}
+
+// mark -> per-build-row 0/1 -> scan -> ordered emit of the build rows
+template <class P>
+static int probe_right(gpue_session* s, const gpue_join_table* t, const P& p,
+                       uint64_t n_rows, int anti, gpue_dbuf* out_build_idx,
+                       uint64_t* count) {
+    DevScratch tmp;
+    CountScan scan;
+    uint64_t br = t->row_count;
+    uint64_t nwords = (br + 1 + 31) / 32;
+    uint32_t nb = grid_for(br);
+    uint32_t* d_bits = nullptr;
+    uint32_t* d_counts = nullptr;
+    uint64_t* d_offsets = nullptr;
+    HIP_CHECK(tmp.alloc(&d_bits, nwords * 4));
+    HIP_CHECK(hipMemsetAsync(d_bits, 0, nwords * 4, s->stream));
+    hipLaunchKernelGGL((k_right_mark<P>), dim3(grid_for(n_rows)), dim3(BLOCK), 0, s->stream,
+                       p, n_rows, d_bits);
+    HIP_CHECK(tmp.alloc(&d_counts, br * 4));
+    int rc = scan.init(s, tmp, br);
+    if (rc != GPUE_OK) return rc;
+    hipLaunchKernelGGL(k_right_row_counts, dim3(nb), dim3(BLOCK), 0, s->stream, d_bits, br,
+                       anti, d_counts);
+    uint64_t total = 0;
+    rc = scan.total(d_counts, &total);
+    if (rc != GPUE_OK) return rc;
+    *count = total;
+    if (out_build_idx && total > 0) {
+        ARG_CHECK(out_build_idx->bytes >= total * 4);
+        HIP_CHECK(tmp.alloc(&d_offsets, br * 8));
+        scan.offsets(d_offsets);
+        hipLaunchKernelGGL(k_right_emit, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
+                           d_offsets, br, (uint32_t*)out_build_idx->ptr);
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+    }
     return GPUE_OK;
+}
+
+// the i32-key table kinds -> their lookup policy: returns f(policy)
+template <class F>
+static int with_i32_policy(const gpue_join_table* t, const gpue_dbuf* probe_keys, F f) {
+    const uint32_t mask = (uint32_t)(t->bucket_size - 1);
+    switch (t->kind) {
+    case gpue_join_table::LINEAR_CHAINED:
+        return f(ProbeLinear{(const uint32_t*)probe_keys->ptr, t->log_bucket_size, mask,
+                             t->first, t->next, t->build_keys});
+    case gpue_join_table::BUCKET_CHAINED:
+        return f(ProbeChained<uint32_t, HashU32>{(const uint32_t*)probe_keys->ptr,
+                                                 HashU32::of(t), t->first, t->next,
+                                                 t->build_keys});
+    case gpue_join_table::DENSE_RANGE_DIRECT:
+        return f(ProbeDense{(const int32_t*)probe_keys->ptr, t->min_key, t->max_key,
+                            t->dense_groups, t->first, t->next});
+    default:
+        return f(ProbeRangeDirect{(const int32_t*)probe_keys->ptr, t->min_key, t->max_key,
+                                  t->first, t->next});
+    }
+}
+
+static ProbeVarchar varchar_policy(const gpue_join_table* t, const gpue_dbuf* pbytes,
+                                   const gpue_dbuf* poffsets) {
+    return ProbeVarchar{(const uint8_t*)pbytes->ptr, (const uint32_t*)poffsets->ptr,
+                        (uint32_t)(t->bucket_size - 1), t->first, t->next, t->key_bytes,
+                        t->key_offsets};
+}
+
+extern "C" {
+int gpue_join_probe_emit_nulls_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
+                                   gpue_dbuf* probe_nulls, uint64_t n_rows, int mode,
+                                   gpue_dbuf* out_probe_idx, gpue_dbuf* out_build_idx,
+                                   uint64_t* match_count);
+}
+
+int gpue_join_probe_emit_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
+                             uint64_t n_rows, gpue_dbuf* out_probe_idx,
+                             gpue_dbuf* out_build_idx, uint64_t* match_count) {
+    return gpue_join_probe_emit_mode_i32(s, t, probe_keys, n_rows, 0, out_probe_idx,
+                                         out_build_idx, match_count);
+}
+
+int gpue_join_probe_emit_mode_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
+                                  uint64_t n_rows, int mode, gpue_dbuf* out_probe_idx,
+                                  gpue_dbuf* out_build_idx, uint64_t* match_count) {
+    ARG_CHECK(s && t && probe_keys && match_count && t->next != nullptr);
+    ARG_CHECK(mode >= 0 && mode <= 3);
+    ARG_CHECK(probe_keys->bytes >= n_rows * 4);
+    return with_i32_policy(t, probe_keys, [&](auto p) {
+        return probe_emit(s, p, n_rows, mode, out_probe_idx, out_build_idx, match_count);
+    });
+}
+
+int gpue_join_probe_emit_nulls_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
+                                   gpue_dbuf* probe_nulls, uint64_t n_rows, int mode,
+                                   gpue_dbuf* out_probe_idx, gpue_dbuf* out_build_idx,
+                                   uint64_t* match_count) {
+    ARG_CHECK(s && t && probe_keys && probe_nulls && match_count);
+    ARG_CHECK(t->kind == gpue_join_table::BUCKET_CHAINED && t->next != nullptr);
+    ARG_CHECK((mode >= 0 && mode <= 3) || mode == 6);
+    ARG_CHECK(probe_nulls->bytes >= n_rows);
+    using P = ProbeChained<uint32_t, HashU32>;
+    return probe_emit(s,
+                      WithNulls<P>{P{(const uint32_t*)probe_keys->ptr, HashU32::of(t), t->first,
+                                     t->next, t->build_keys},
+                                   (const uint8_t*)probe_nulls->ptr},
+                      n_rows, mode, out_probe_idx, out_build_idx, match_count);
+}
+
+int gpue_join_probe_emit_mode_u64(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
+                                  uint64_t n_rows, int mode, gpue_dbuf* out_probe_idx,
+                                  gpue_dbuf* out_build_idx, uint64_t* match_count) {
+    ARG_CHECK(s && t && probe_keys && match_count);
+    ARG_CHECK(t->kind == gpue_join_table::BUCKET_CHAINED64);
+    ARG_CHECK(mode >= 0 && mode <= 3);
+    ARG_CHECK(probe_keys->bytes >= n_rows * 8);
+    return probe_emit(s,
+                      ProbeChained<uint64_t, HashU64>{(const uint64_t*)probe_keys->ptr,
+                                                      HashU64::of(t), t->first, t->next,
+                                                      t->build_keys64},
+                      n_rows, mode, out_probe_idx, out_build_idx, match_count);
 }
 
 int gpue_join_probe_emit_mode_u128(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
@@ -3961,40 +3808,45 @@ int gpue_join_probe_emit_mode_u128(gpue_session* s, gpue_join_table* t, gpue_dbu
     ARG_CHECK(t->kind == gpue_join_table::BUCKET_CHAINED128);
     ARG_CHECK(mode >= 0 && mode <= 3);
     ARG_CHECK(probe_keys->bytes >= n_rows * 16);
-    uint32_t nb = grid_for(n_rows);
-    uint64_t tile = (n_rows + nb - 1) / nb;
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bsums = nullptr;
-    uint64_t* d_offsets = nullptr;
-    HIP_CHECK(hipMalloc(&d_counts, n_rows * 4));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * 8));
-    hipLaunchKernelGGL(k_probe_count_u128, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const ulonglong2*)probe_keys->ptr, n_rows,
-                       (uint32_t)(t->bucket_size - 1), t->first, t->next, t->build_keys128,
-                       mode, d_counts);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                       n_rows, tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    *match_count = total;
-    if (out_probe_idx && out_build_idx && total > 0) {
-        ARG_CHECK(out_probe_idx->bytes >= total * 4 && out_build_idx->bytes >= total * 4);
-        HIP_CHECK(hipMalloc(&d_offsets, n_rows * 8));
-        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                           n_rows, tile, d_bsums, d_offsets);
-        hipLaunchKernelGGL(k_probe_emit_u128, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const ulonglong2*)probe_keys->ptr, n_rows,
-                           (uint32_t)(t->bucket_size - 1), t->first, t->next,
-                           t->build_keys128, mode, d_counts, d_offsets,
-                           (uint32_t*)out_probe_idx->ptr, (uint32_t*)out_build_idx->ptr);
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_offsets);
-    }
-    (void)hipFree(d_counts);
-    (void)hipFree(d_bsums);
-    return GPUE_OK;
+    return probe_emit(s,
+                      ProbeChained<ulonglong2, HashU128>{(const ulonglong2*)probe_keys->ptr,
+                                                         HashU128::of(t), t->first, t->next,
+                                                         t->build_keys128},
+                      n_rows, mode, out_probe_idx, out_build_idx, match_count);
+}
+
+int gpue_join_probe_emit_varchar_nulls(gpue_session* s, gpue_join_table* t, gpue_dbuf* pbytes,
+                                       gpue_dbuf* poffsets, gpue_dbuf* pnulls,
+                                       uint64_t n_rows, int mode, gpue_dbuf* out_probe_idx,
+                                       gpue_dbuf* out_build_idx, uint64_t* match_count) {
+    ARG_CHECK(s && t && pbytes && poffsets && match_count);
+    ARG_CHECK((mode >= 0 && mode <= 3) || mode == 6);
+    ARG_CHECK(t->kind == gpue_join_table::VARCHAR);
+    ARG_CHECK(poffsets->bytes >= (n_rows + 1) * 4);
+    ProbeVarchar p = varchar_policy(t, pbytes, poffsets);
+    if (pnulls)
+        return probe_emit(s, WithNulls<ProbeVarchar>{p, (const uint8_t*)pnulls->ptr}, n_rows,
+                          mode, out_probe_idx, out_build_idx, match_count);
+    return probe_emit(s, p, n_rows, mode, out_probe_idx, out_build_idx, match_count);
+}
+
+int gpue_join_probe_right_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
+                              uint64_t n_rows, int anti, gpue_dbuf* out_build_idx,
+                              uint64_t* count) {
+    ARG_CHECK(s && t && probe_keys && count && t->next != nullptr);
+    return with_i32_policy(t, probe_keys, [&](auto p) {
+        return probe_right(s, t, p, n_rows, anti, out_build_idx, count);
+    });
+}
+
+int gpue_join_probe_right_varchar(gpue_session* s, gpue_join_table* t, gpue_dbuf* pbytes,
+                                  gpue_dbuf* poffsets, uint64_t n_rows, int anti,
+                                  gpue_dbuf* out_build_idx, uint64_t* count) {
+    ARG_CHECK(s && t && pbytes && poffsets && count);
+    ARG_CHECK(t->kind == gpue_join_table::VARCHAR);
+    if (out_build_idx) ARG_CHECK(out_build_idx->bytes >= t->row_count * 4);
+    return probe_right(s, t, varchar_policy(t, pbytes, poffsets), n_rows, anti, out_build_idx,
+                       count);
 }
 
 // SERIALIZED_FIXED_SIZE_LARGEINT packing for two 8-byte key columns
@@ -4105,334 +3957,6 @@ int gpue_sbf_test_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n, gpue_dbuf* d
                        (const int32_t*)keys->ptr, n, (const uint32_t*)directory->ptr,
                        log_num_buckets, (uint8_t*)out->ptr);
     HIP_CHECK(hipGetLastError());
-    return GPUE_OK;
-}
-
-// RIGHT SEMI/ANTI over Slice keys: probe pass marks matched BUILD rows
-// (atomicOr into a bitset), then compact matched/unmatched build rows.
-__global__ void k_probe_mark_vc(const uint8_t* __restrict__ pbytes,
-                                const uint32_t* __restrict__ poffsets, uint64_t n,
-                                uint32_t bucket_mask, const uint32_t* __restrict__ first,
-                                const uint32_t* __restrict__ next,
-                                const uint8_t* __restrict__ bbytes,
-                                const uint32_t* __restrict__ boffsets,
-                                uint32_t* __restrict__ matched_bits) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t len = poffsets[i + 1] - poffsets[i];
-        uint32_t b = crc_hash_32_dev(pbytes + poffsets[i], len, 0x811C9DC5u) & bucket_mask;
-        for (uint32_t j = first[b]; j != 0; j = next[j])
-            if (slice_eq(bbytes + boffsets[j], boffsets[j + 1] - boffsets[j],
-                         pbytes + poffsets[i], len))
-                atomicOr(&matched_bits[j >> 5], 1u << (j & 31));
-    }
-}
-
-extern "C" int gpue_join_probe_right_varchar(gpue_session* s, gpue_join_table* t,
-                                             gpue_dbuf* pbytes, gpue_dbuf* poffsets,
-                                             uint64_t n_rows, int anti,
-                                             gpue_dbuf* out_build_idx, uint64_t* count);
-__global__ void k_right_emit_bits(const uint32_t* __restrict__ matched_bits,
-                                  uint64_t build_rows, int anti,
-                                  unsigned long long* __restrict__ cursor,
-                                  uint32_t* __restrict__ out) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = 1 + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j <= build_rows;
-         j += stride) {
-        uint32_t hit = (matched_bits[j >> 5] >> (j & 31)) & 1u;
-        if ((anti && !hit) || (!anti && hit)) {
-            unsigned long long pos = atomicAdd(cursor, 1ull);
-            if (out) out[pos] = (uint32_t)j;
-        }
-    }
-}
-
-int gpue_join_probe_right_varchar(gpue_session* s, gpue_join_table* t, gpue_dbuf* pbytes,
-                                  gpue_dbuf* poffsets, uint64_t n_rows, int anti,
-                                  gpue_dbuf* out_build_idx, uint64_t* count) {
-    ARG_CHECK(s && t && pbytes && poffsets && count);
-    ARG_CHECK(t->kind == gpue_join_table::VARCHAR);
-    uint64_t nwords = (t->row_count + 1 + 31) / 32;
-    uint32_t* d_bits = nullptr;
-    unsigned long long* d_cursor = nullptr;
-    HIP_CHECK(hipMalloc(&d_bits, nwords * 4));
-    HIP_CHECK(hipMalloc(&d_cursor, 8));
-    HIP_CHECK(hipMemsetAsync(d_bits, 0, nwords * 4, s->stream));
-    HIP_CHECK(hipMemsetAsync(d_cursor, 0, 8, s->stream));
-    hipLaunchKernelGGL(k_probe_mark_vc, dim3(grid_for(n_rows)), dim3(BLOCK), 0, s->stream,
-                       (const uint8_t*)pbytes->ptr, (const uint32_t*)poffsets->ptr, n_rows,
-                       (uint32_t)(t->bucket_size - 1), t->first, t->next, t->key_bytes,
-                       t->key_offsets, d_bits);
-    if (out_build_idx) {
-        ARG_CHECK(out_build_idx->bytes >= t->row_count * 4);
-        hipLaunchKernelGGL(k_right_emit_bits, dim3(grid_for(t->row_count)), dim3(BLOCK), 0,
-                           s->stream, d_bits, t->row_count, anti, d_cursor,
-                           (uint32_t*)out_build_idx->ptr);
-    } else {
-        hipLaunchKernelGGL(k_right_emit_bits, dim3(grid_for(t->row_count)), dim3(BLOCK), 0,
-                           s->stream, d_bits, t->row_count, anti, d_cursor, nullptr);
-    }
-    unsigned long long c = 0;
-    HIP_CHECK(hipMemcpyAsync(&c, d_cursor, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    (void)hipFree(d_bits);
-    (void)hipFree(d_cursor);
-    *count = c;
-    return GPUE_OK;
-}
-
-// Nullable probe (lookup_init is_nulls path + per-type semantics): a null
-// probe key matches nothing — INNER/SEMI emit nothing for it, ANTI/OUTER
-// emit the unmatched (i, 0) row.
-__global__ void k_probe_count_bc_nulls(const uint32_t* __restrict__ probe_keys,
-                                       const uint8_t* __restrict__ is_nulls, uint64_t n,
-                                       uint32_t log_bucket_size,
-                                       const uint32_t* __restrict__ first,
-                                       const uint32_t* __restrict__ next,
-                                       const uint32_t* __restrict__ build_keys, int mode,
-                                       uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t c = 0;
-        if (!is_nulls[i]) {
-            uint32_t k = probe_keys[i];
-            uint32_t b = first[join_hash_u32(k, log_bucket_size)];
-            while (b != 0) {
-                c += (build_keys[b] == k);
-                b = next[b];
-            }
-        } else if (mode == 6) {
-            // NULL_AWARE_LEFT_ANTI (the NOT IN lowering,
-            // join_hash_map.hpp:1225-1240): null probe rows are EXCLUDED —
-            // NULL NOT IN (...) is never true — where plain LEFT_ANTI emits
-            // them as unmatched
-            row_counts[i] = 0;
-            continue;
-        }
-        row_counts[i] = join_mode_count(c, mode == 6 ? 2 : mode);
-    }
-}
-
-__global__ void k_probe_emit_bc_nulls(const uint32_t* __restrict__ probe_keys,
-                                      const uint8_t* __restrict__ is_nulls, uint64_t n,
-                                      uint32_t log_bucket_size,
-                                      const uint32_t* __restrict__ first,
-                                      const uint32_t* __restrict__ next,
-                                      const uint32_t* __restrict__ build_keys, int mode,
-                                      const uint32_t* __restrict__ row_counts,
-                                      const uint64_t* __restrict__ row_offsets,
-                                      uint32_t* __restrict__ out_probe,
-                                      uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    if (mode == 6) mode = 2; // null-aware anti: null rows already have count 0
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        if (row_counts[i] == 0) continue;
-        uint64_t pos = row_offsets[i];
-        bool any = false;
-        if (!is_nulls[i]) {
-            uint32_t k = probe_keys[i];
-            uint32_t b = first[join_hash_u32(k, log_bucket_size)];
-            while (b != 0) {
-                if (build_keys[b] == k) {
-                    any = true;
-                    if (mode != 2) {
-                        out_probe[pos] = (uint32_t)i;
-                        out_build[pos] = b;
-                        pos++;
-                    }
-                    if (mode == 1 || mode == 2) break;
-                }
-                b = next[b];
-            }
-        }
-        if (!any && (mode == 2 || mode == 3)) {
-            out_probe[pos] = (uint32_t)i;
-            out_build[pos] = 0;
-        }
-    }
-}
-
-extern "C" int gpue_join_probe_emit_nulls_i32(gpue_session* s, gpue_join_table* t,
-                                              gpue_dbuf* probe_keys, gpue_dbuf* probe_nulls,
-                                              uint64_t n_rows, int mode,
-                                              gpue_dbuf* out_probe_idx,
-                                              gpue_dbuf* out_build_idx, uint64_t* match_count);
-int gpue_join_probe_emit_nulls_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
-                                   gpue_dbuf* probe_nulls, uint64_t n_rows, int mode,
-                                   gpue_dbuf* out_probe_idx, gpue_dbuf* out_build_idx,
-                                   uint64_t* match_count) {
-    ARG_CHECK(s && t && probe_keys && probe_nulls && match_count);
-    ARG_CHECK(t->kind == gpue_join_table::BUCKET_CHAINED && t->next != nullptr);
-    ARG_CHECK(probe_nulls->bytes >= n_rows);
-    uint32_t nb = grid_for(n_rows);
-    uint64_t tile = (n_rows + nb - 1) / nb;
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bsums = nullptr;
-    uint64_t* d_offsets = nullptr;
-    HIP_CHECK(hipMalloc(&d_counts, n_rows * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * sizeof(uint64_t)));
-    hipLaunchKernelGGL(k_probe_count_bc_nulls, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint32_t*)probe_keys->ptr, (const uint8_t*)probe_nulls->ptr,
-                       n_rows, t->log_bucket_size, t->first, t->next, t->build_keys, mode,
-                       d_counts);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                       n_rows, tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    *match_count = total;
-    if (out_probe_idx && out_build_idx && total > 0) {
-        ARG_CHECK(out_probe_idx->bytes >= total * 4 && out_build_idx->bytes >= total * 4);
-        HIP_CHECK(hipMalloc(&d_offsets, n_rows * sizeof(uint64_t)));
-        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                           n_rows, tile, d_bsums, d_offsets);
-        hipLaunchKernelGGL(k_probe_emit_bc_nulls, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)probe_keys->ptr,
-                           (const uint8_t*)probe_nulls->ptr, n_rows, t->log_bucket_size,
-                           t->first, t->next, t->build_keys, mode, d_counts, d_offsets,
-                           (uint32_t*)out_probe_idx->ptr, (uint32_t*)out_build_idx->ptr);
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_offsets);
-    }
-    (void)hipFree(d_counts);
-    (void)hipFree(d_bsums);
-    return GPUE_OK;
-}
-
-// RIGHT SEMI/ANTI (join_hash_map.hpp _probe_from_ht_for_right_*): the probe
-// pass marks matched BUILD rows; output = matched (semi) / unmatched (anti)
-// build rows.
-__global__ void k_right_mark_rd(const int32_t* __restrict__ probe_keys, uint64_t n,
-                                int64_t mn, int64_t mx, const uint32_t* __restrict__ first,
-                                const uint32_t* __restrict__ next,
-                                uint32_t* __restrict__ matched_bits) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        int32_t k = probe_keys[i];
-        if (k < mn || k > mx) continue;
-        uint32_t b = first[k - mn];
-        while (b != 0) {
-            atomicOr(&matched_bits[b >> 5], 1u << (b & 31));
-            b = next[b];
-        }
-    }
-}
-
-// DENSE_RANGE_DIRECT right-mark: rank/select head + chain walk, no compare
-__global__ void k_right_mark_dense(const int32_t* __restrict__ probe_keys, uint64_t n,
-                                   int64_t mn, int64_t mx,
-                                   const uint2* __restrict__ groups,
-                                   const uint32_t* __restrict__ first,
-                                   const uint32_t* __restrict__ next,
-                                   uint32_t* __restrict__ matched_bits) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t b = dense_head(probe_keys, i, mn, mx, groups, first);
-        while (b != 0) {
-            atomicOr(&matched_bits[b >> 5], 1u << (b & 31));
-            b = next[b];
-        }
-    }
-}
-
-__global__ void k_right_mark_keys(const uint32_t* __restrict__ probe_keys, uint64_t n,
-                                  int is_linear, uint32_t log_bucket_size,
-                                  uint32_t bucket_mask, const uint32_t* __restrict__ first,
-                                  const uint32_t* __restrict__ next,
-                                  const uint32_t* __restrict__ build_keys,
-                                  uint32_t* __restrict__ matched_bits) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        uint32_t k = probe_keys[i];
-        uint32_t b = is_linear
-                         ? lc_lookup_head(k, log_bucket_size, bucket_mask, first, build_keys)
-                         : first[join_hash_u32(k, log_bucket_size)];
-        while (b != 0) {
-            if (is_linear || build_keys[b] == k)
-                atomicOr(&matched_bits[b >> 5], 1u << (b & 31));
-            b = next[b];
-        }
-    }
-}
-
-__global__ void k_right_row_counts(const uint32_t* __restrict__ matched_bits,
-                                   uint64_t build_rows, int anti,
-                                   uint32_t* __restrict__ row_counts) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < build_rows;
-         j += stride) {
-        uint32_t b = (uint32_t)j + 1; // build rows are 1-based
-        uint32_t m = (matched_bits[b >> 5] >> (b & 31)) & 1u;
-        row_counts[j] = anti ? (1u - m) : m;
-    }
-}
-
-__global__ void k_right_emit(const uint32_t* __restrict__ row_counts,
-                             const uint64_t* __restrict__ row_offsets, uint64_t build_rows,
-                             uint32_t* __restrict__ out_build) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < build_rows;
-         j += stride)
-        if (row_counts[j]) out_build[row_offsets[j]] = (uint32_t)j + 1;
-}
-
-extern "C" int gpue_join_probe_right_i32(gpue_session* s, gpue_join_table* t,
-                                         gpue_dbuf* probe_keys, uint64_t n_rows, int anti,
-                                         gpue_dbuf* out_build_idx, uint64_t* count);
-int gpue_join_probe_right_i32(gpue_session* s, gpue_join_table* t, gpue_dbuf* probe_keys,
-                              uint64_t n_rows, int anti, gpue_dbuf* out_build_idx,
-                              uint64_t* count) {
-    ARG_CHECK(s && t && probe_keys && count && t->next != nullptr);
-    uint64_t nwords = (t->row_count + 1 + 31) / 32;
-    uint32_t* d_bits = nullptr;
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bsums = nullptr;
-    uint64_t* d_offsets = nullptr;
-    HIP_CHECK(hipMalloc(&d_bits, nwords * 4));
-    HIP_CHECK(hipMemsetAsync(d_bits, 0, nwords * 4, s->stream));
-    if (t->kind == gpue_join_table::RANGE_DIRECT) {
-        hipLaunchKernelGGL(k_right_mark_rd, dim3(grid_for(n_rows)), dim3(BLOCK), 0, s->stream,
-                           (const int32_t*)probe_keys->ptr, n_rows, t->min_key, t->max_key,
-                           t->first, t->next, d_bits);
-    } else if (t->kind == gpue_join_table::DENSE_RANGE_DIRECT) {
-        hipLaunchKernelGGL(k_right_mark_dense, dim3(grid_for(n_rows)), dim3(BLOCK), 0,
-                           s->stream, (const int32_t*)probe_keys->ptr, n_rows, t->min_key,
-                           t->max_key, t->dense_groups, t->first, t->next, d_bits);
-    } else {
-        hipLaunchKernelGGL(k_right_mark_keys, dim3(grid_for(n_rows)), dim3(BLOCK), 0,
-                           s->stream, (const uint32_t*)probe_keys->ptr, n_rows,
-                           t->kind == gpue_join_table::LINEAR_CHAINED ? 1 : 0,
-                           t->log_bucket_size, (uint32_t)(t->bucket_size - 1), t->first,
-                           t->next, t->build_keys, d_bits);
-    }
-    uint64_t br = t->row_count;
-    uint32_t nb = grid_for(br);
-    uint64_t tile = (br + nb - 1) / nb;
-    HIP_CHECK(hipMalloc(&d_counts, br * 4));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * 8));
-    hipLaunchKernelGGL(k_right_row_counts, dim3(nb), dim3(BLOCK), 0, s->stream, d_bits, br,
-                       anti, d_counts);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts, br,
-                       tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    *count = total;
-    if (out_build_idx && total > 0) {
-        ARG_CHECK(out_build_idx->bytes >= total * 4);
-        HIP_CHECK(hipMalloc(&d_offsets, br * 8));
-        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts, br,
-                           tile, d_bsums, d_offsets);
-        hipLaunchKernelGGL(k_right_emit, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                           d_offsets, br, (uint32_t*)out_build_idx->ptr);
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_offsets);
-    }
-    (void)hipFree(d_bits);
-    (void)hipFree(d_counts);
-    (void)hipFree(d_bsums);
     return GPUE_OK;
 }
 
@@ -9057,46 +8581,37 @@ int gpue_page_decode_binary_prefix(gpue_session* s, gpue_dbuf* page, uint64_t n_
         return GPUE_ERR_ARG;
     }
     if (n == 0) return GPUE_OK;
+    DevScratch tmp;
+    CountScan scan;
     uint32_t* d_lens = nullptr;
     uint2* d_meta = nullptr;
-    uint64_t *d_bsums = nullptr, *d_off64 = nullptr;
-    HIP_CHECK(hipMalloc(&d_lens, (uint64_t)n * 4));
-    HIP_CHECK(hipMalloc(&d_meta, (uint64_t)n * 8));
-    uint32_t nb = grid_for(n);
-    uint64_t tile = ((uint64_t)n + nb - 1) / nb;
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * 8));
-    HIP_CHECK(hipMalloc(&d_off64, ((uint64_t)n + 1) * 8));
+    uint64_t* d_off64 = nullptr;
+    HIP_CHECK(tmp.alloc(&d_lens, (uint64_t)n * 4));
+    HIP_CHECK(tmp.alloc(&d_meta, (uint64_t)n * 8));
+    HIP_CHECK(tmp.alloc(&d_off64, ((uint64_t)n + 1) * 8));
+    int rc = scan.init(s, tmp, n);
+    if (rc != GPUE_OK) return rc;
     hipLaunchKernelGGL(k_bprefix_scan, dim3(grid_for(nrestart)), dim3(BLOCK), 0, s->stream,
                        (const uint8_t*)page->ptr, restart_tab, nrestart, n, d_lens, d_meta);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_lens, n,
-                       tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_lens, n, tile,
-                       d_bsums, d_off64);
     uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    int rc = GPUE_OK;
+    rc = scan.total(d_lens, &total);
+    if (rc != GPUE_OK) return rc;
     if (out_bytes->bytes < total && total > 0) {
         snprintf(g_err, sizeof(g_err), "binary_prefix: out_bytes %llu < total %llu",
                  (unsigned long long)out_bytes->bytes, (unsigned long long)total);
-        rc = GPUE_ERR_ARG;
-    } else {
-        // d_off64 holds per-entry EXCLUSIVE offsets; write u32 offsets[ n+1 ]
-        HIP_CHECK(hipMemcpyAsync(d_off64 + n, d_bsums + nb, 8, hipMemcpyDeviceToDevice,
-                                 s->stream));
-        hipLaunchKernelGGL(k_bprefix_offsets, dim3(grid_for(n + 1)), dim3(BLOCK), 0,
-                           s->stream, d_off64, n, (uint32_t*)out_offsets->ptr);
-        hipLaunchKernelGGL(k_bprefix_fill, dim3(grid_for(nrestart)), dim3(BLOCK), 0,
-                           s->stream, (const uint8_t*)page->ptr, nrestart, n, d_meta,
-                           (const uint32_t*)out_offsets->ptr, (uint8_t*)out_bytes->ptr);
-        HIP_CHECK(hipStreamSynchronize(s->stream));
+        return GPUE_ERR_ARG;
     }
-    (void)hipFree(d_lens);
-    (void)hipFree(d_meta);
-    (void)hipFree(d_bsums);
-    (void)hipFree(d_off64);
-    return rc;
+    // d_off64 holds per-entry EXCLUSIVE offsets, then the total; write u32 offsets[ n+1 ]
+    scan.offsets(d_off64);
+    HIP_CHECK(hipMemcpyAsync(d_off64 + n, scan.d_total(), 8, hipMemcpyDeviceToDevice,
+                             s->stream));
+    hipLaunchKernelGGL(k_bprefix_offsets, dim3(grid_for(n + 1)), dim3(BLOCK), 0, s->stream,
+                       d_off64, n, (uint32_t*)out_offsets->ptr);
+    hipLaunchKernelGGL(k_bprefix_fill, dim3(grid_for(nrestart)), dim3(BLOCK), 0, s->stream,
+                       (const uint8_t*)page->ptr, nrestart, n, d_meta,
+                       (const uint32_t*)out_offsets->ptr, (uint8_t*)out_bytes->ptr);
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GPUE_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -10643,7 +10158,11 @@ static int asof_build_impl(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* asof,
     ARG_CHECK(s && keys && asof && out && row_count > 0 && row_count + 1 < (1ull << 31));
     ARG_CHECK(opcode >= GPUE_ASOF_LT && opcode <= GPUE_ASOF_GE);
     ARG_CHECK(keys->bytes >= (row_count + 1) * 4 && asof->bytes >= (row_count + 1) * 8);
-    gpue_asof_table* t = new gpue_asof_table();
+    struct Deleter {
+        void operator()(gpue_asof_table* p) const { (void)gpue_asof_table_destroy(p); }
+    };
+    std::unique_ptr<gpue_asof_table, Deleter> own(new gpue_asof_table());
+    gpue_asof_table* t = own.get();
     t->s = s;
     t->opcode = opcode;
     t->row_count = row_count;
@@ -10656,14 +10175,15 @@ static int asof_build_impl(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* asof,
     uint32_t* d_caps = nullptr;
     uint32_t* d_occ = nullptr;
     uint32_t* d_misc = nullptr; // occ cursor + scatter cursors
-    uint64_t* d_bsums = nullptr;
     uint64_t* d_offsets = nullptr;
+    DevScratch tmp;
+    CountScan scan;
     HIP_CHECK(hipMalloc(&t->slots, t->n_slots * 8));
     HIP_CHECK(hipMalloc(&t->meta, t->n_slots * 8));
-    HIP_CHECK(hipMalloc(&d_counts, t->n_slots * 4));
-    HIP_CHECK(hipMalloc(&d_caps, t->n_slots * 4));
-    HIP_CHECK(hipMalloc(&d_occ, row_count * 4));
-    HIP_CHECK(hipMalloc(&d_misc, (t->n_slots + 1) * 4));
+    HIP_CHECK(tmp.alloc(&d_counts, t->n_slots * 4));
+    HIP_CHECK(tmp.alloc(&d_caps, t->n_slots * 4));
+    HIP_CHECK(tmp.alloc(&d_occ, row_count * 4));
+    HIP_CHECK(tmp.alloc(&d_misc, (t->n_slots + 1) * 4));
     HIP_CHECK(hipMemsetAsync(t->slots, 0, t->n_slots * 8, s->stream));
     HIP_CHECK(hipMemsetAsync(d_counts, 0, t->n_slots * 4, s->stream));
     HIP_CHECK(hipMemsetAsync(d_misc, 0, (t->n_slots + 1) * 4, s->stream));
@@ -10673,24 +10193,19 @@ static int asof_build_impl(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* asof,
                        t->slots, d_counts, d_occ, d_misc);
     // pow2 arena capacities, block-scanned to segment starts
     uint32_t nb_slots = grid_for(t->n_slots);
-    uint64_t tile = (t->n_slots + nb_slots - 1) / nb_slots;
-    HIP_CHECK(hipMalloc(&d_bsums, (nb_slots + 1) * 8));
-    HIP_CHECK(hipMalloc(&d_offsets, t->n_slots * 8));
+    HIP_CHECK(tmp.alloc(&d_offsets, t->n_slots * 8));
+    int rc = scan.init(s, tmp, t->n_slots);
+    if (rc != GPUE_OK) return rc;
     hipLaunchKernelGGL(k_asof_caps, dim3(nb_slots), dim3(BLOCK), 0, s->stream, d_counts,
                        t->n_slots, d_caps);
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb_slots), dim3(BLOCK), 0, s->stream, d_caps,
-                       t->n_slots, tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb_slots);
-    hipLaunchKernelGGL(k_scan_offsets, dim3(nb_slots), dim3(BLOCK), 0, s->stream, d_caps,
-                       t->n_slots, tile, d_bsums, d_offsets);
-    hipLaunchKernelGGL(k_asof_pack_meta, dim3(nb_slots), dim3(BLOCK), 0, s->stream,
-                       d_offsets, d_counts, t->n_slots, t->meta);
     uint64_t arena = 0; // padded total <= 2*row_count
     uint32_t n_occ = 0;
-    HIP_CHECK(hipMemcpyAsync(&arena, d_bsums + nb_slots, 8, hipMemcpyDeviceToHost,
-                             s->stream));
     HIP_CHECK(hipMemcpyAsync(&n_occ, d_misc, 4, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
+    rc = scan.total(d_caps, &arena); // syncs: n_occ is valid too
+    if (rc != GPUE_OK) return rc;
+    scan.offsets(d_offsets);
+    hipLaunchKernelGGL(k_asof_pack_meta, dim3(nb_slots), dim3(BLOCK), 0, s->stream,
+                       d_offsets, d_counts, t->n_slots, t->meta);
     HIP_CHECK(hipMalloc(&t->asof_vals, (arena ? arena : 1) * 8));
     HIP_CHECK(hipMalloc(&t->asof_rows, (arena ? arena : 1) * 4));
     hipLaunchKernelGGL(k_asof_scatter, dim3(nb_rows), dim3(BLOCK), 0, s->stream,
@@ -10716,13 +10231,7 @@ static int asof_build_impl(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* asof,
     t->slots = nullptr;
     (void)hipFree(t->meta);
     t->meta = nullptr;
-    (void)hipFree(d_counts);
-    (void)hipFree(d_caps);
-    (void)hipFree(d_occ);
-    (void)hipFree(d_misc);
-    (void)hipFree(d_bsums);
-    (void)hipFree(d_offsets);
-    *out = t;
+    *out = own.release();
     return GPUE_OK;
 }
 
@@ -10739,6 +10248,17 @@ int gpue_asof_build_nulls_i32(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* asof,
                            opcode, out);
 }
 
+// ASOF opcode -> the probe kernels' template argument: f(integral_constant<int, OP>)
+template <class F>
+static void asof_dispatch(int opcode, F f) {
+    switch (opcode) {
+    case GPUE_ASOF_LT: f(std::integral_constant<int, 0>()); break;
+    case GPUE_ASOF_LE: f(std::integral_constant<int, 1>()); break;
+    case GPUE_ASOF_GT: f(std::integral_constant<int, 2>()); break;
+    default: f(std::integral_constant<int, 3>()); break;
+    }
+}
+
 static int asof_probe_impl(gpue_session* s, gpue_asof_table* t, gpue_dbuf* probe_keys,
                            gpue_dbuf* probe_asof, const uint8_t* d_pnulls, uint64_t n_rows,
                            int mode, gpue_dbuf* out_probe_idx, gpue_dbuf* out_build_idx,
@@ -10746,92 +10266,29 @@ static int asof_probe_impl(gpue_session* s, gpue_asof_table* t, gpue_dbuf* probe
     ARG_CHECK(s && t && probe_keys && probe_asof && match_count);
     ARG_CHECK(mode == GPUE_JOIN_INNER || mode == GPUE_JOIN_LEFT_OUTER);
     ARG_CHECK(probe_keys->bytes >= n_rows * 4 && probe_asof->bytes >= n_rows * 8);
-    uint32_t nb = grid_for(n_rows);
-    uint64_t tile = (n_rows + nb - 1) / nb;
+    const int32_t* pk = (const int32_t*)probe_keys->ptr;
+    const int64_t* pa = (const int64_t*)probe_asof->ptr;
     uint32_t cmask = (uint32_t)(t->n_cslots - 1);
-    uint32_t* d_counts = nullptr;
-    uint64_t* d_bsums = nullptr;
-    uint64_t* d_offsets = nullptr;
-    HIP_CHECK(hipMalloc(&d_counts, (n_rows ? n_rows : 1) * 4));
-    HIP_CHECK(hipMalloc(&d_bsums, (nb + 1) * 8));
-    switch (t->opcode) {
-    case GPUE_ASOF_LT:
-        hipLaunchKernelGGL(k_asof_probe_count<0>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const int32_t*)probe_keys->ptr, (const int64_t*)probe_asof->ptr, d_pnulls,
-                           n_rows, t->log_cslots, cmask, t->cslots, t->asof_vals,
-                           t->asof_rows, mode, d_counts);
-        break;
-    case GPUE_ASOF_LE:
-        hipLaunchKernelGGL(k_asof_probe_count<1>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const int32_t*)probe_keys->ptr, (const int64_t*)probe_asof->ptr, d_pnulls,
-                           n_rows, t->log_cslots, cmask, t->cslots, t->asof_vals,
-                           t->asof_rows, mode, d_counts);
-        break;
-    case GPUE_ASOF_GT:
-        hipLaunchKernelGGL(k_asof_probe_count<2>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const int32_t*)probe_keys->ptr, (const int64_t*)probe_asof->ptr, d_pnulls,
-                           n_rows, t->log_cslots, cmask, t->cslots, t->asof_vals,
-                           t->asof_rows, mode, d_counts);
-        break;
-    default:
-        hipLaunchKernelGGL(k_asof_probe_count<3>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const int32_t*)probe_keys->ptr, (const int64_t*)probe_asof->ptr, d_pnulls,
-                           n_rows, t->log_cslots, cmask, t->cslots, t->asof_vals,
-                           t->asof_rows, mode, d_counts);
-        break;
-    }
-    hipLaunchKernelGGL(k_block_sums_u32, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                       n_rows, tile, d_bsums);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bsums, nb);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, d_bsums + nb, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    *match_count = total;
-    if (out_probe_idx && out_build_idx && total > 0) {
-        ARG_CHECK(out_probe_idx->bytes >= total * 4 && out_build_idx->bytes >= total * 4);
-        HIP_CHECK(hipMalloc(&d_offsets, n_rows * 8));
-        hipLaunchKernelGGL(k_scan_offsets, dim3(nb), dim3(BLOCK), 0, s->stream, d_counts,
-                           n_rows, tile, d_bsums, d_offsets);
-        switch (t->opcode) {
-        case GPUE_ASOF_LT:
-            hipLaunchKernelGGL(k_asof_probe_emit<0>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                               (const int32_t*)probe_keys->ptr,
-                               (const int64_t*)probe_asof->ptr, d_pnulls, n_rows, t->log_cslots, cmask,
-                               t->cslots, t->asof_vals, t->asof_rows, mode,
-                               d_counts, d_offsets, (uint32_t*)out_probe_idx->ptr,
-                               (uint32_t*)out_build_idx->ptr);
-            break;
-        case GPUE_ASOF_LE:
-            hipLaunchKernelGGL(k_asof_probe_emit<1>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                               (const int32_t*)probe_keys->ptr,
-                               (const int64_t*)probe_asof->ptr, d_pnulls, n_rows, t->log_cslots, cmask,
-                               t->cslots, t->asof_vals, t->asof_rows, mode,
-                               d_counts, d_offsets, (uint32_t*)out_probe_idx->ptr,
-                               (uint32_t*)out_build_idx->ptr);
-            break;
-        case GPUE_ASOF_GT:
-            hipLaunchKernelGGL(k_asof_probe_emit<2>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                               (const int32_t*)probe_keys->ptr,
-                               (const int64_t*)probe_asof->ptr, d_pnulls, n_rows, t->log_cslots, cmask,
-                               t->cslots, t->asof_vals, t->asof_rows, mode,
-                               d_counts, d_offsets, (uint32_t*)out_probe_idx->ptr,
-                               (uint32_t*)out_build_idx->ptr);
-            break;
-        default:
-            hipLaunchKernelGGL(k_asof_probe_emit<3>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                               (const int32_t*)probe_keys->ptr,
-                               (const int64_t*)probe_asof->ptr, d_pnulls, n_rows, t->log_cslots, cmask,
-                               t->cslots, t->asof_vals, t->asof_rows, mode,
-                               d_counts, d_offsets, (uint32_t*)out_probe_idx->ptr,
-                               (uint32_t*)out_build_idx->ptr);
-            break;
-        }
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_offsets);
-    }
-    (void)hipFree(d_counts);
-    (void)hipFree(d_bsums);
-    return GPUE_OK;
+    return probe_count_scan_emit(
+        s, n_rows, out_probe_idx, out_build_idx, match_count,
+        [&](uint32_t nb, uint32_t* d_counts) {
+            asof_dispatch(t->opcode, [&](auto op) {
+                hipLaunchKernelGGL((k_asof_probe_count<decltype(op)::value>), dim3(nb),
+                                   dim3(BLOCK), 0, s->stream, pk, pa, d_pnulls, n_rows,
+                                   t->log_cslots, cmask, t->cslots, t->asof_vals,
+                                   t->asof_rows, mode, d_counts);
+            });
+        },
+        [&](uint32_t nb, const uint32_t* d_counts, const uint64_t* d_offsets,
+            uint32_t* out_probe, uint32_t* out_build) {
+            asof_dispatch(t->opcode, [&](auto op) {
+                hipLaunchKernelGGL((k_asof_probe_emit<decltype(op)::value>), dim3(nb),
+                                   dim3(BLOCK), 0, s->stream, pk, pa, d_pnulls, n_rows,
+                                   t->log_cslots, cmask, t->cslots, t->asof_vals,
+                                   t->asof_rows, mode, d_counts, d_offsets, out_probe,
+                                   out_build);
+            });
+        });
 }
 
 int gpue_asof_probe_emit_i32(gpue_session* s, gpue_asof_table* t, gpue_dbuf* probe_keys,

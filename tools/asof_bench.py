@@ -28,7 +28,7 @@ def main():
     rng = np.random.default_rng(42)
     rc = 10_000_000          # build rows
     n_keys = 1_000_000       # ~10 entries/key -> ~3-4 search steps
-    n_probe = 600_000_000    # lineorder scale
+    n_probe = int(sys.argv[1]) if len(sys.argv) > 1 else 600_000_000  # lineorder scale
 
     bk = np.concatenate([[0], rng.integers(1, n_keys + 1, rc)]).astype(np.int32)
     ba = np.concatenate([[0], rng.integers(-10**12, 10**12, rc)]).astype(np.int64)
