@@ -2511,17 +2511,14 @@ int gpue_dict_decode_binary(gpue_session* s, gpue_dbuf* dict_bytes, gpue_dbuf* d
 // conjuncts touch fewer rows; final compaction applies a pending filter.
 // ops: 0 EQ(lo), 1 LT(hi), 2 BETWEEN[lo,hi].
 // ---------------------------------------------------------------------------
-__global__ void k_gather_u32(const uint32_t* __restrict__ in,
-                             const uint32_t* __restrict__ idx, uint64_t n,
-                             uint32_t* __restrict__ out);
-
-__global__ void k_eval_pred_i32(const int32_t* __restrict__ col, uint64_t n, int op,
-                                int32_t lo, int32_t hi, uint8_t* __restrict__ filter,
-                                unsigned long long* __restrict__ true_count) {
+template <class T>
+__global__ void k_eval_pred(const T* __restrict__ col, uint64_t n, int op, T lo, T hi,
+                            uint8_t* __restrict__ filter,
+                            unsigned long long* __restrict__ true_count) {
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     unsigned long long local = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        int32_t v = col[i];
+        T v = col[i];
         uint8_t pass = op == 0 ? (v == lo) : op == 1 ? (v < hi) : (v >= lo && v <= hi);
         uint8_t merged = filter[i] & pass;
         filter[i] = merged;
@@ -2562,72 +2559,72 @@ __global__ void k_mask_emit_idx(const uint8_t* __restrict__ filter, uint64_t n,
     }
 }
 
-__global__ void k_eval_pred_i64(const int64_t* __restrict__ col, uint64_t n, int op,
-                                int64_t lo, int64_t hi, uint8_t* __restrict__ filter,
-                                unsigned long long* __restrict__ true_count) {
+// row gather by index: the compaction below, and gpue_gather_u32 / _u64
+__global__ void k_gather_u32(const uint32_t* __restrict__ in,
+                             const uint32_t* __restrict__ idx, uint64_t n,
+                             uint32_t* __restrict__ out) {
     uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    unsigned long long local = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        int64_t v = col[i];
-        uint8_t pass = op == 0 ? (v == lo) : op == 1 ? (v < hi) : (v >= lo && v <= hi);
-        uint8_t merged = filter[i] & pass;
-        filter[i] = merged;
-        local += merged;
-    }
-    for (int off = 32; off > 0; off >>= 1)
-        local += __shfl_down(local, off, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && local)
-        atomicAdd(true_count, local);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = in[idx[i]];
 }
 
 __global__ void k_gather_u64(const uint64_t* __restrict__ in,
                              const uint32_t* __restrict__ idx, uint64_t n,
-                             uint64_t* __restrict__ out);
+                             uint64_t* __restrict__ out) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = in[idx[i]];
+}
 
-extern "C" int gpue_eval_conjuncts_i32(gpue_session* s, gpue_dbuf** cols, int n_cols,
-                                       uint64_t n_rows, const int32_t* pred_col,
-                                       const int32_t* pred_op, const int32_t* pred_lo,
-                                       const int32_t* pred_hi, int n_preds,
-                                       uint64_t* out_rows);
-int gpue_eval_conjuncts_i32(gpue_session* s, gpue_dbuf** cols, int n_cols, uint64_t n_rows,
-                            const int32_t* pred_col, const int32_t* pred_op,
-                            const int32_t* pred_lo, const int32_t* pred_hi, int n_preds,
-                            uint64_t* out_rows) {
+// T is the column and literal type (int32_t / int64_t). d_filter and d_tc
+// live in `call` for the whole call, each compaction's buffers in a
+// DevScratch of its own, so every return frees what it allocated.
+template <class T>
+static int eval_conjuncts_impl(gpue_session* s, gpue_dbuf** cols, int n_cols, uint64_t n_rows,
+                               const int32_t* pred_col, const int32_t* pred_op,
+                               const T* pred_lo, const T* pred_hi, int n_preds,
+                               uint64_t* out_rows) {
     ARG_CHECK(s && cols && n_cols > 0 && pred_col && pred_op && pred_lo && pred_hi &&
               out_rows);
     uint64_t n = n_rows;
+    DevScratch call;
     uint8_t* d_filter = nullptr;
     unsigned long long* d_tc = nullptr;
-    HIP_CHECK(hipMalloc(&d_filter, n_rows ? n_rows : 1));
-    HIP_CHECK(hipMalloc(&d_tc, 8));
+    HIP_CHECK(call.alloc(&d_filter, n_rows ? n_rows : 1));
+    HIP_CHECK(call.alloc(&d_tc, 8));
     HIP_CHECK(hipMemsetAsync(d_filter, 1, n_rows ? n_rows : 1, s->stream));
     uint64_t zero_count = 0;
 
     auto compact_all = [&](uint64_t keep) -> int {
-        uint32_t nb = grid_for(n);
-        uint64_t tile = (n + nb - 1) / nb;
-        uint64_t* d_bs = nullptr;
-        uint32_t* d_idx = nullptr;
-        int32_t* d_tmp = nullptr;
-        HIP_CHECK(hipMalloc(&d_bs, (nb + 1) * 8));
-        HIP_CHECK(hipMalloc(&d_idx, keep * 4));
-        HIP_CHECK(hipMalloc(&d_tmp, keep * 4));
-        hipLaunchKernelGGL(k_mask_block_counts, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           d_filter, n, tile, d_bs);
-        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bs, nb);
-        hipLaunchKernelGGL(k_mask_emit_idx, dim3(nb), dim3(BLOCK), 0, s->stream, d_filter,
-                           n, tile, d_bs, d_idx);
-        for (int k = 0; k < n_cols; k++) {
-            hipLaunchKernelGGL(k_gather_u32, dim3(grid_stream(keep)), dim3(BLOCK), 0,
-                               s->stream, (const uint32_t*)cols[k]->ptr, d_idx, keep,
-                               (uint32_t*)d_tmp);
-            HIP_CHECK(hipMemcpyAsync(cols[k]->ptr, d_tmp, keep * 4,
-                                     hipMemcpyDeviceToDevice, s->stream));
-        }
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_bs);
-        (void)hipFree(d_idx);
-        (void)hipFree(d_tmp);
+        {
+            uint32_t nb = grid_for(n);
+            uint64_t tile = (n + nb - 1) / nb;
+            DevScratch tmp;
+            uint64_t* d_bs = nullptr;
+            uint32_t* d_idx = nullptr;
+            T* d_tmp = nullptr;
+            HIP_CHECK(tmp.alloc(&d_bs, (nb + 1) * 8));
+            HIP_CHECK(tmp.alloc(&d_idx, keep * 4));
+            HIP_CHECK(tmp.alloc(&d_tmp, keep * sizeof(T)));
+            hipLaunchKernelGGL(k_mask_block_counts, dim3(nb), dim3(BLOCK), 0, s->stream,
+                               d_filter, n, tile, d_bs);
+            hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bs, nb);
+            hipLaunchKernelGGL(k_mask_emit_idx, dim3(nb), dim3(BLOCK), 0, s->stream,
+                               d_filter, n, tile, d_bs, d_idx);
+            for (int k = 0; k < n_cols; k++) {
+                if constexpr (sizeof(T) == 4)
+                    hipLaunchKernelGGL(k_gather_u32, dim3(grid_stream(keep)), dim3(BLOCK), 0,
+                                       s->stream, (const uint32_t*)cols[k]->ptr, d_idx, keep,
+                                       (uint32_t*)d_tmp);
+                else
+                    hipLaunchKernelGGL(k_gather_u64, dim3(grid_stream(keep)), dim3(BLOCK), 0,
+                                       s->stream, (const uint64_t*)cols[k]->ptr, d_idx, keep,
+                                       (uint64_t*)d_tmp);
+                HIP_CHECK(hipMemcpyAsync(cols[k]->ptr, d_tmp, keep * sizeof(T),
+                                         hipMemcpyDeviceToDevice, s->stream));
+            }
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+        } // tmp is freed here, before the next conjunct is enqueued
         n = keep;
         HIP_CHECK(hipMemsetAsync(d_filter, 1, n ? n : 1, s->stream));
         zero_count = 0;
@@ -2637,9 +2634,9 @@ int gpue_eval_conjuncts_i32(gpue_session* s, gpue_dbuf** cols, int n_cols, uint6
     for (int p = 0; p < n_preds && n > 0; p++) {
         ARG_CHECK(pred_col[p] >= 0 && pred_col[p] < n_cols);
         HIP_CHECK(hipMemsetAsync(d_tc, 0, 8, s->stream));
-        hipLaunchKernelGGL(k_eval_pred_i32, dim3(grid_stream(n)), dim3(BLOCK), 0, s->stream,
-                           (const int32_t*)cols[pred_col[p]]->ptr, n, pred_op[p],
-                           pred_lo[p], pred_hi[p], d_filter, d_tc);
+        hipLaunchKernelGGL(k_eval_pred<T>, dim3(grid_stream(n)), dim3(BLOCK), 0, s->stream,
+                           (const T*)cols[pred_col[p]]->ptr, n, pred_op[p], pred_lo[p],
+                           pred_hi[p], d_filter, d_tc);
         unsigned long long tc = 0;
         HIP_CHECK(hipMemcpyAsync(&tc, d_tc, 8, hipMemcpyDeviceToHost, s->stream));
         HIP_CHECK(hipStreamSynchronize(s->stream));
@@ -2658,87 +2655,24 @@ int gpue_eval_conjuncts_i32(gpue_session* s, gpue_dbuf** cols, int n_cols, uint6
         int rc = compact_all(n - zero_count);
         if (rc != GPUE_OK) return rc;
     }
-    (void)hipFree(d_filter);
-    (void)hipFree(d_tc);
     *out_rows = n;
     return GPUE_OK;
 }
 
-extern "C" int gpue_eval_conjuncts_i64(gpue_session* s, gpue_dbuf** cols, int n_cols,
-                                       uint64_t n_rows, const int32_t* pred_col,
-                                       const int32_t* pred_op, const int64_t* pred_lo,
-                                       const int64_t* pred_hi, int n_preds,
-                                       uint64_t* out_rows);
+int gpue_eval_conjuncts_i32(gpue_session* s, gpue_dbuf** cols, int n_cols, uint64_t n_rows,
+                            const int32_t* pred_col, const int32_t* pred_op,
+                            const int32_t* pred_lo, const int32_t* pred_hi, int n_preds,
+                            uint64_t* out_rows) {
+    return eval_conjuncts_impl<int32_t>(s, cols, n_cols, n_rows, pred_col, pred_op, pred_lo,
+                                        pred_hi, n_preds, out_rows);
+}
+
 int gpue_eval_conjuncts_i64(gpue_session* s, gpue_dbuf** cols, int n_cols, uint64_t n_rows,
                             const int32_t* pred_col, const int32_t* pred_op,
                             const int64_t* pred_lo, const int64_t* pred_hi, int n_preds,
                             uint64_t* out_rows) {
-    ARG_CHECK(s && cols && n_cols > 0 && pred_col && pred_op && pred_lo && pred_hi &&
-              out_rows);
-    uint64_t n = n_rows;
-    uint8_t* d_filter = nullptr;
-    unsigned long long* d_tc = nullptr;
-    HIP_CHECK(hipMalloc(&d_filter, n_rows ? n_rows : 1));
-    HIP_CHECK(hipMalloc(&d_tc, 8));
-    HIP_CHECK(hipMemsetAsync(d_filter, 1, n_rows ? n_rows : 1, s->stream));
-    uint64_t zero_count = 0;
-
-    auto compact_all = [&](uint64_t keep) -> int {
-        uint32_t nb = grid_for(n);
-        uint64_t tile = (n + nb - 1) / nb;
-        uint64_t* d_bs = nullptr;
-        uint32_t* d_idx = nullptr;
-        int64_t* d_tmp = nullptr;
-        HIP_CHECK(hipMalloc(&d_bs, (nb + 1) * 8));
-        HIP_CHECK(hipMalloc(&d_idx, keep * 4));
-        HIP_CHECK(hipMalloc(&d_tmp, keep * 8));
-        hipLaunchKernelGGL(k_mask_block_counts, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           d_filter, n, tile, d_bs);
-        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1), 0, s->stream, d_bs, nb);
-        hipLaunchKernelGGL(k_mask_emit_idx, dim3(nb), dim3(BLOCK), 0, s->stream, d_filter,
-                           n, tile, d_bs, d_idx);
-        for (int k = 0; k < n_cols; k++) {
-            hipLaunchKernelGGL(k_gather_u64, dim3(grid_stream(keep)), dim3(BLOCK), 0,
-                               s->stream, (const uint64_t*)cols[k]->ptr, d_idx, keep,
-                               (uint64_t*)d_tmp);
-            HIP_CHECK(hipMemcpyAsync(cols[k]->ptr, d_tmp, keep * 8,
-                                     hipMemcpyDeviceToDevice, s->stream));
-        }
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        (void)hipFree(d_bs);
-        (void)hipFree(d_idx);
-        (void)hipFree(d_tmp);
-        n = keep;
-        HIP_CHECK(hipMemsetAsync(d_filter, 1, n ? n : 1, s->stream));
-        zero_count = 0;
-        return GPUE_OK;
-    };
-
-    for (int p = 0; p < n_preds && n > 0; p++) {
-        ARG_CHECK(pred_col[p] >= 0 && pred_col[p] < n_cols);
-        HIP_CHECK(hipMemsetAsync(d_tc, 0, 8, s->stream));
-        hipLaunchKernelGGL(k_eval_pred_i64, dim3(grid_stream(n)), dim3(BLOCK), 0, s->stream,
-                           (const int64_t*)cols[pred_col[p]]->ptr, n, pred_op[p],
-                           pred_lo[p], pred_hi[p], d_filter, d_tc);
-        unsigned long long tc = 0;
-        HIP_CHECK(hipMemcpyAsync(&tc, d_tc, 8, hipMemcpyDeviceToHost, s->stream));
-        HIP_CHECK(hipStreamSynchronize(s->stream));
-        if (tc == 0) { n = 0; break; }
-        zero_count = n - tc;
-        uint64_t prune_threshold = n * 8 / 10 > 1024 ? n * 8 / 10 : 1024;
-        if (zero_count > prune_threshold) {
-            int rc = compact_all(tc);
-            if (rc != GPUE_OK) return rc;
-        }
-    }
-    if (n > 0 && zero_count > 0) {
-        int rc = compact_all(n - zero_count);
-        if (rc != GPUE_OK) return rc;
-    }
-    (void)hipFree(d_filter);
-    (void)hipFree(d_tc);
-    *out_rows = n;
-    return GPUE_OK;
+    return eval_conjuncts_impl<int64_t>(s, cols, n_cols, n_rows, pred_col, pred_op, pred_lo,
+                                        pred_hi, n_preds, out_rows);
 }
 
 // ---------------------------------------------------------------------------
@@ -5812,21 +5746,58 @@ __device__ static inline uint32_t fnv_u64(uint64_t key, uint32_t seed) {
 }
 
 static constexpr uint32_t MAX_CH = 64;
-__global__ void k_partition_scan(const uint32_t* __restrict__ hist, uint32_t nb,
-                                 uint32_t nch, uint64_t* __restrict__ offsets);
 
-template <int HV> // 0 = FNV (default/back-compat), 1 = xxh3 (version 1)
-__global__ void k_partition_hist(const uint32_t* __restrict__ keys, uint64_t n, uint64_t tile,
-                                 uint32_t nch, uint32_t* __restrict__ block_hist) {
+// Partition key policies: the key column pointer(s), passed by value in the
+// kernel arguments, and the exchange hash of row i. They are the only thing
+// that differs between key shapes; the kernels and drivers below are shared.
+template <int HV> // 0 = FNV (default/back-compat), 1 = xxh3 (version 1), 2 = crc (bucket shuffle)
+struct PartU32 {
+    const uint32_t* __restrict__ keys;
+    __device__ uint32_t hash(uint64_t i) const {
+        return HV == 2   ? zlib_crc32_u32(keys[i], 0)
+               : HV == 1 ? (uint32_t)xxh3_64_u32(keys[i], XXH3_SEED_32)
+                         : fnv_u32(keys[i], 0x811C9DC5u);
+    }
+};
+
+// BIGINT key (FNV over the 8 LE bytes, reference fnv_hash on an int64 key column)
+struct PartU64 {
+    const uint64_t* __restrict__ keys;
+    __device__ uint32_t hash(uint64_t i) const { return fnv_u64(keys[i], 0x811C9DC5u); }
+};
+
+// Multi-column partition key: the exchange sink seeds FNV_SEED then CHAINS
+// fnv_hash per partition column, each column using the running hash as its
+// seed (exchange_sink_operator.cpp:611-617). Two-int32 variant.
+struct Part2xI32 {
+    const int32_t* __restrict__ a;
+    const int32_t* __restrict__ b;
+    __device__ uint32_t hash(uint64_t i) const {
+        return fnv_u32((uint32_t)b[i], fnv_u32((uint32_t)a[i], 0x811C9DC5u));
+    }
+};
+
+// varchar (BinaryColumn) partition key: the exchange hashes the slice bytes
+// (fnv_hash over BinaryColumn, FNV_SEED)
+struct PartVarchar {
+    const uint8_t* __restrict__ bytes;
+    const uint32_t* __restrict__ offsets;
+    __device__ uint32_t hash(uint64_t i) const {
+        uint32_t h = 0x811C9DC5u;
+        for (uint32_t b = offsets[i]; b < offsets[i + 1]; b++) h = (bytes[b] ^ h) * 16777619u;
+        return h;
+    }
+};
+
+template <class P>
+__global__ void k_partition_hist(P p, uint64_t n, uint64_t tile, uint32_t nch,
+                                 uint32_t* __restrict__ block_hist) {
     __shared__ uint32_t h[MAX_CH];
     for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x) h[c] = 0;
     __syncthreads();
     uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
     for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint32_t hash = HV == 2   ? zlib_crc32_u32(keys[i], 0)
-                        : HV == 1 ? (uint32_t)xxh3_64_u32(keys[i], XXH3_SEED_32)
-                                  : fnv_u32(keys[i], 0x811C9DC5u);
-        uint32_t ch = (uint32_t)(((uint64_t)hash * nch) >> 32);
+        uint32_t ch = (uint32_t)(((uint64_t)p.hash(i) * nch) >> 32);
         atomicAdd(&h[ch], 1u);
     }
     __syncthreads();
@@ -5834,9 +5805,9 @@ __global__ void k_partition_hist(const uint32_t* __restrict__ keys, uint64_t n, 
         block_hist[(uint64_t)blockIdx.x * nch + c] = h[c];
 }
 
-template <int HV>
-__global__ void k_partition_emit(const uint32_t* __restrict__ keys, uint64_t n, uint64_t tile,
-                                 uint32_t nch, const uint64_t* __restrict__ block_offsets,
+template <class P>
+__global__ void k_partition_emit(P p, uint64_t n, uint64_t tile, uint32_t nch,
+                                 const uint64_t* __restrict__ block_offsets,
                                  uint32_t* __restrict__ row_indexes) {
     __shared__ uint64_t cursor[MAX_CH];
     for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x)
@@ -5844,217 +5815,10 @@ __global__ void k_partition_emit(const uint32_t* __restrict__ keys, uint64_t n, 
     __syncthreads();
     uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
     for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint32_t hash = HV == 2   ? zlib_crc32_u32(keys[i], 0)
-                        : HV == 1 ? (uint32_t)xxh3_64_u32(keys[i], XXH3_SEED_32)
-                                  : fnv_u32(keys[i], 0x811C9DC5u);
-        uint32_t ch = (uint32_t)(((uint64_t)hash * nch) >> 32);
+        uint32_t ch = (uint32_t)(((uint64_t)p.hash(i) * nch) >> 32);
         uint64_t pos = atomicAdd((unsigned long long*)&cursor[ch], 1ull);
         row_indexes[pos] = (uint32_t)i;
     }
-}
-
-// Multi-column partition key: the exchange sink seeds FNV_SEED then CHAINS
-// fnv_hash per partition column, each column using the running hash as its
-// seed (exchange_sink_operator.cpp:611-617). Two-int32 variant.
-__global__ void k_partition_hist_2xi32(const int32_t* __restrict__ a,
-                                       const int32_t* __restrict__ b, uint64_t n,
-                                       uint64_t tile, uint32_t nch,
-                                       uint32_t* __restrict__ block_hist) {
-    __shared__ uint32_t h[MAX_CH];
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x) h[c] = 0;
-    __syncthreads();
-    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint32_t hash = fnv_u32((uint32_t)b[i], fnv_u32((uint32_t)a[i], 0x811C9DC5u));
-        uint32_t ch = (uint32_t)(((uint64_t)hash * nch) >> 32);
-        atomicAdd(&h[ch], 1u);
-    }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x)
-        block_hist[(uint64_t)blockIdx.x * nch + c] = h[c];
-}
-
-__global__ void k_partition_emit_2xi32(const int32_t* __restrict__ a,
-                                       const int32_t* __restrict__ b, uint64_t n,
-                                       uint64_t tile, uint32_t nch,
-                                       const uint64_t* __restrict__ block_offsets,
-                                       uint32_t* __restrict__ row_indexes) {
-    __shared__ uint64_t cursor[MAX_CH];
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x)
-        cursor[c] = block_offsets[(uint64_t)blockIdx.x * nch + c];
-    __syncthreads();
-    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint32_t hash = fnv_u32((uint32_t)b[i], fnv_u32((uint32_t)a[i], 0x811C9DC5u));
-        uint32_t ch = (uint32_t)(((uint64_t)hash * nch) >> 32);
-        uint64_t pos = atomicAdd((unsigned long long*)&cursor[ch], 1ull);
-        row_indexes[pos] = (uint32_t)i;
-    }
-}
-
-__global__ void k_partition_hist64(const uint64_t* __restrict__ keys, uint64_t n,
-                                   uint64_t tile, uint32_t nch,
-                                   uint32_t* __restrict__ block_hist) {
-    __shared__ uint32_t h[MAX_CH];
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x) h[c] = 0;
-    __syncthreads();
-    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint32_t ch = (uint32_t)(((uint64_t)fnv_u64(keys[i], 0x811C9DC5u) * nch) >> 32);
-        atomicAdd(&h[ch], 1u);
-    }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x)
-        block_hist[(uint64_t)blockIdx.x * nch + c] = h[c];
-}
-
-__global__ void k_partition_emit64(const uint64_t* __restrict__ keys, uint64_t n,
-                                   uint64_t tile, uint32_t nch,
-                                   const uint64_t* __restrict__ block_offsets,
-                                   uint32_t* __restrict__ row_indexes) {
-    __shared__ uint64_t cursor[MAX_CH];
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x)
-        cursor[c] = block_offsets[(uint64_t)blockIdx.x * nch + c];
-    __syncthreads();
-    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint32_t ch = (uint32_t)(((uint64_t)fnv_u64(keys[i], 0x811C9DC5u) * nch) >> 32);
-        uint64_t pos = atomicAdd((unsigned long long*)&cursor[ch], 1ull);
-        row_indexes[pos] = (uint32_t)i;
-    }
-}
-
-// BIGINT-key variant (FNV over the 8 LE bytes, reference fnv_hash on an
-// int64 key column)
-extern "C" int gpue_partition_i64(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
-                                  uint64_t* start_points_out, gpue_dbuf* row_indexes_out);
-int gpue_partition_i64(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
-                       uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
-    ARG_CHECK(s && keys && start_points_out && row_indexes_out);
-    ARG_CHECK(nch >= 1 && nch <= MAX_CH);
-    ARG_CHECK(keys->bytes >= n * 8 && row_indexes_out->bytes >= n * 4);
-    uint32_t nb = grid_for(n);
-    uint64_t tile = (n + nb - 1) / nb;
-    uint32_t* d_hist = nullptr;
-    uint64_t* d_off = nullptr;
-    HIP_CHECK(hipMalloc(&d_hist, (uint64_t)nb * nch * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_partition_hist64, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint64_t*)keys->ptr, n, tile, nch, d_hist);
-    uint32_t* h_hist = (uint32_t*)malloc((uint64_t)nb * nch * sizeof(uint32_t));
-    uint64_t* h_off = (uint64_t*)malloc((uint64_t)nb * nch * sizeof(uint64_t));
-    HIP_CHECK(hipMemcpyAsync(h_hist, d_hist, (uint64_t)nb * nch * sizeof(uint32_t),
-                             hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    uint64_t acc = 0;
-    for (uint32_t c = 0; c < nch; c++) {
-        start_points_out[c] = acc;
-        for (uint32_t b = 0; b < nb; b++) {
-            h_off[(uint64_t)b * nch + c] = acc;
-            acc += h_hist[(uint64_t)b * nch + c];
-        }
-    }
-    start_points_out[nch] = acc;
-    HIP_CHECK(hipMalloc(&d_off, (uint64_t)nb * nch * sizeof(uint64_t)));
-    HIP_CHECK(hipMemcpyAsync(d_off, h_off, (uint64_t)nb * nch * sizeof(uint64_t),
-                             hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_partition_emit64, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint64_t*)keys->ptr, n, tile, nch, d_off,
-                       (uint32_t*)row_indexes_out->ptr);
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    (void)hipFree(d_hist);
-    (void)hipFree(d_off);
-    free(h_hist);
-    free(h_off);
-    return GPUE_OK;
-}
-
-// async i64 form (device-side scan, no host round-trip) — see
-// gpue_partition_i32_async
-extern "C" int gpue_partition_i64_async(gpue_session* s, gpue_dbuf* keys, uint64_t n,
-                                        uint32_t nch, gpue_dbuf* row_indexes_out,
-                                        gpue_dbuf* scratch);
-int gpue_partition_i64_async(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
-                             gpue_dbuf* row_indexes_out, gpue_dbuf* scratch) {
-    ARG_CHECK(s && keys && row_indexes_out && scratch);
-    ARG_CHECK(nch >= 1 && nch <= MAX_CH);
-    ARG_CHECK(keys->bytes >= n * 8 && row_indexes_out->bytes >= n * 4);
-    uint32_t nb = grid_for(n);
-    uint64_t tile = (n + nb - 1) / nb;
-    ARG_CHECK(scratch->bytes >= (uint64_t)nb * nch * 12);
-    uint32_t* d_hist = (uint32_t*)scratch->ptr;
-    uint64_t* d_off = (uint64_t*)((uint8_t*)scratch->ptr + (uint64_t)nb * nch * 4);
-    hipLaunchKernelGGL(k_partition_hist64, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint64_t*)keys->ptr, n, tile, nch, d_hist);
-    hipLaunchKernelGGL(k_partition_scan, dim3(1), dim3(64), 0, s->stream, d_hist, nb, nch,
-                       d_off);
-    hipLaunchKernelGGL(k_partition_emit64, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint64_t*)keys->ptr, n, tile, nch, d_off,
-                       (uint32_t*)row_indexes_out->ptr);
-    HIP_CHECK(hipGetLastError());
-    return GPUE_OK;
-}
-
-static int partition_i32_impl(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
-                              uint64_t* start_points_out, gpue_dbuf* row_indexes_out,
-                              int hash_version) {
-    ARG_CHECK(s && keys && start_points_out && row_indexes_out);
-    ARG_CHECK(nch >= 1 && nch <= MAX_CH);
-    ARG_CHECK(keys->bytes >= n * 4 && row_indexes_out->bytes >= n * 4);
-    uint32_t nb = grid_for(n);
-    uint64_t tile = (n + nb - 1) / nb;
-    uint32_t* d_hist = nullptr;
-    uint64_t* d_off = nullptr;
-    HIP_CHECK(hipMalloc(&d_hist, (uint64_t)nb * nch * sizeof(uint32_t)));
-    if (hash_version == 2)
-        hipLaunchKernelGGL(k_partition_hist<2>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)keys->ptr, n, tile, nch, d_hist);
-    else if (hash_version == 1)
-        hipLaunchKernelGGL(k_partition_hist<1>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)keys->ptr, n, tile, nch, d_hist);
-    else
-        hipLaunchKernelGGL(k_partition_hist<0>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)keys->ptr, n, tile, nch, d_hist);
-    // host scan in channel-major order -> per-(block,channel) start offsets
-    uint32_t* h_hist = (uint32_t*)malloc((uint64_t)nb * nch * sizeof(uint32_t));
-    uint64_t* h_off = (uint64_t*)malloc((uint64_t)nb * nch * sizeof(uint64_t));
-    HIP_CHECK(hipMemcpyAsync(h_hist, d_hist, (uint64_t)nb * nch * sizeof(uint32_t),
-                             hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    uint64_t acc = 0;
-    for (uint32_t c = 0; c < nch; c++) {
-        start_points_out[c] = acc;
-        for (uint32_t b = 0; b < nb; b++) {
-            h_off[(uint64_t)b * nch + c] = acc;
-            acc += h_hist[(uint64_t)b * nch + c];
-        }
-    }
-    start_points_out[nch] = acc;
-    HIP_CHECK(hipMalloc(&d_off, (uint64_t)nb * nch * sizeof(uint64_t)));
-    HIP_CHECK(hipMemcpyAsync(d_off, h_off, (uint64_t)nb * nch * sizeof(uint64_t),
-                             hipMemcpyHostToDevice, s->stream));
-    if (hash_version == 2)
-        hipLaunchKernelGGL(k_partition_emit<2>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)keys->ptr, n, tile, nch, d_off,
-                           (uint32_t*)row_indexes_out->ptr);
-    else if (hash_version == 1)
-        hipLaunchKernelGGL(k_partition_emit<1>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)keys->ptr, n, tile, nch, d_off,
-                           (uint32_t*)row_indexes_out->ptr);
-    else
-        hipLaunchKernelGGL(k_partition_emit<0>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                           (const uint32_t*)keys->ptr, n, tile, nch, d_off,
-                           (uint32_t*)row_indexes_out->ptr);
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    (void)hipFree(d_hist);
-    (void)hipFree(d_off);
-    free(h_hist);
-    free(h_off);
-    return GPUE_OK;
-}
-
-int gpue_partition_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
-                       uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
-    return partition_i32_impl(s, keys, n, nch, start_points_out, row_indexes_out, 0);
 }
 
 // Device-side channel-major exclusive scan of the per-(block,channel)
@@ -6074,120 +5838,28 @@ __global__ void k_partition_scan(const uint32_t* __restrict__ hist, uint32_t nb,
         }
 }
 
-template <int HV>
-static int partition_i32_async_impl(gpue_session* s, gpue_dbuf* keys, uint64_t n,
-                                    uint32_t nch, gpue_dbuf* row_indexes_out,
-                                    gpue_dbuf* scratch) {
-    ARG_CHECK(s && keys && row_indexes_out && scratch);
+// Sync form: hist -> host scan in channel-major order (it also yields the
+// start points the caller gets back) -> emit. The entry has checked its key
+// buffers and that row_indexes_out is non-null.
+template <class P>
+static int partition_sync(gpue_session* s, P p, uint64_t n, uint32_t nch,
+                          uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
     ARG_CHECK(nch >= 1 && nch <= MAX_CH);
-    ARG_CHECK(keys->bytes >= n * 4 && row_indexes_out->bytes >= n * 4);
+    ARG_CHECK(row_indexes_out->bytes >= n * 4);
     uint32_t nb = grid_for(n);
     uint64_t tile = (n + nb - 1) / nb;
-    // scratch holds hist (u32) + offsets (u64) per (block, channel)
-    ARG_CHECK(scratch->bytes >= (uint64_t)nb * nch * 12);
-    uint32_t* d_hist = (uint32_t*)scratch->ptr;
-    uint64_t* d_off = (uint64_t*)((uint8_t*)scratch->ptr + (uint64_t)nb * nch * 4);
-    hipLaunchKernelGGL(k_partition_hist<HV>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint32_t*)keys->ptr, n, tile, nch, d_hist);
-    hipLaunchKernelGGL(k_partition_scan, dim3(1), dim3(64), 0, s->stream, d_hist, nb, nch,
-                       d_off);
-    hipLaunchKernelGGL(k_partition_emit<HV>, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint32_t*)keys->ptr, n, tile, nch, d_off,
-                       (uint32_t*)row_indexes_out->ptr);
-    HIP_CHECK(hipGetLastError());
-    return GPUE_OK;
-}
-
-extern "C" int gpue_partition_i32_async(gpue_session* s, gpue_dbuf* keys, uint64_t n,
-                                        uint32_t nch, gpue_dbuf* row_indexes_out,
-                                        gpue_dbuf* scratch);
-int gpue_partition_i32_async(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
-                             gpue_dbuf* row_indexes_out, gpue_dbuf* scratch) {
-    return partition_i32_async_impl<0>(s, keys, n, nch, row_indexes_out, scratch);
-}
-
-// version-1 exchange hash (xxh3) partition — exchange_sink_operator.cpp:
-// 604-610's `_exchange_hash_function_version == 1` branch
-extern "C" int gpue_partition_xxh3_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n,
-                                       uint32_t nch, uint64_t* start_points_out,
-                                       gpue_dbuf* row_indexes_out);
-int gpue_partition_xxh3_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
-                            uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
-    return partition_i32_impl(s, keys, n, nch, start_points_out, row_indexes_out, 1);
-}
-
-// bucket-shuffle hash path (zlib crc32, seed 0) — the third exchange hash
-// (exchange_sink_operator.cpp:617-622)
-extern "C" int gpue_partition_crc_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n,
-                                      uint32_t nch, uint64_t* start_points_out,
-                                      gpue_dbuf* row_indexes_out);
-int gpue_partition_crc_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
-                           uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
-    return partition_i32_impl(s, keys, n, nch, start_points_out, row_indexes_out, 2);
-}
-
-// varchar (BinaryColumn) partition key: the exchange hashes the slice bytes
-// (fnv_hash over BinaryColumn, FNV_SEED) — same counting-sort layout
-__global__ void k_partition_hist_vc(const uint8_t* __restrict__ bytes,
-                                    const uint32_t* __restrict__ offsets, uint64_t n,
-                                    uint64_t tile, uint32_t nch,
-                                    uint32_t* __restrict__ block_hist) {
-    __shared__ uint32_t h[MAX_CH];
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x) h[c] = 0;
-    __syncthreads();
-    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint32_t hash = 0x811C9DC5u;
-        for (uint32_t b = offsets[i]; b < offsets[i + 1]; b++)
-            hash = (bytes[b] ^ hash) * 16777619u;
-        uint32_t ch = (uint32_t)(((uint64_t)hash * nch) >> 32);
-        atomicAdd(&h[ch], 1u);
-    }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x)
-        block_hist[(uint64_t)blockIdx.x * nch + c] = h[c];
-}
-
-__global__ void k_partition_emit_vc(const uint8_t* __restrict__ bytes,
-                                    const uint32_t* __restrict__ offsets, uint64_t n,
-                                    uint64_t tile, uint32_t nch,
-                                    const uint64_t* __restrict__ block_offsets,
-                                    uint32_t* __restrict__ row_indexes) {
-    __shared__ uint64_t cursor[MAX_CH];
-    for (uint32_t c = threadIdx.x; c < nch; c += blockDim.x)
-        cursor[c] = block_offsets[(uint64_t)blockIdx.x * nch + c];
-    __syncthreads();
-    uint64_t lo = (uint64_t)blockIdx.x * tile, hi = min(lo + tile, n);
-    for (uint64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        uint32_t hash = 0x811C9DC5u;
-        for (uint32_t b = offsets[i]; b < offsets[i + 1]; b++)
-            hash = (bytes[b] ^ hash) * 16777619u;
-        uint32_t ch = (uint32_t)(((uint64_t)hash * nch) >> 32);
-        uint64_t pos = atomicAdd((unsigned long long*)&cursor[ch], 1ull);
-        row_indexes[pos] = (uint32_t)i;
-    }
-}
-
-extern "C" int gpue_partition_varchar(gpue_session* s, gpue_dbuf* bytes, gpue_dbuf* offsets,
-                                      uint64_t n, uint32_t nch, uint64_t* start_points_out,
-                                      gpue_dbuf* row_indexes_out);
-int gpue_partition_varchar(gpue_session* s, gpue_dbuf* bytes, gpue_dbuf* offsets,
-                           uint64_t n, uint32_t nch, uint64_t* start_points_out,
-                           gpue_dbuf* row_indexes_out) {
-    ARG_CHECK(s && bytes && offsets && start_points_out && row_indexes_out);
-    ARG_CHECK(nch >= 1 && nch <= MAX_CH);
-    ARG_CHECK(offsets->bytes >= (n + 1) * 4 && row_indexes_out->bytes >= n * 4);
-    uint32_t nb = grid_for(n);
-    uint64_t tile = (n + nb - 1) / nb;
+    uint64_t cells = (uint64_t)nb * nch; // one per (block, channel)
+    std::vector<uint32_t> h_hist; // declared before tmp: its hipFree drains the
+    std::vector<uint64_t> h_off;  // stream before these copy targets go away
+    DevScratch tmp;
     uint32_t* d_hist = nullptr;
     uint64_t* d_off = nullptr;
-    HIP_CHECK(hipMalloc(&d_hist, (uint64_t)nb * nch * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_partition_hist_vc, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint8_t*)bytes->ptr, (const uint32_t*)offsets->ptr, n, tile,
+    HIP_CHECK(tmp.alloc(&d_hist, cells * sizeof(uint32_t)));
+    hipLaunchKernelGGL(k_partition_hist<P>, dim3(nb), dim3(BLOCK), 0, s->stream, p, n, tile,
                        nch, d_hist);
-    uint32_t* h_hist = (uint32_t*)malloc((uint64_t)nb * nch * sizeof(uint32_t));
-    uint64_t* h_off = (uint64_t*)malloc((uint64_t)nb * nch * sizeof(uint64_t));
-    HIP_CHECK(hipMemcpyAsync(h_hist, d_hist, (uint64_t)nb * nch * sizeof(uint32_t),
+    h_hist.resize(cells);
+    h_off.resize(cells);
+    HIP_CHECK(hipMemcpyAsync(h_hist.data(), d_hist, cells * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, s->stream));
     HIP_CHECK(hipStreamSynchronize(s->stream));
     uint64_t acc = 0;
@@ -6199,63 +5871,107 @@ int gpue_partition_varchar(gpue_session* s, gpue_dbuf* bytes, gpue_dbuf* offsets
         }
     }
     start_points_out[nch] = acc;
-    HIP_CHECK(hipMalloc(&d_off, (uint64_t)nb * nch * sizeof(uint64_t)));
-    HIP_CHECK(hipMemcpyAsync(d_off, h_off, (uint64_t)nb * nch * sizeof(uint64_t),
+    HIP_CHECK(tmp.alloc(&d_off, cells * sizeof(uint64_t)));
+    HIP_CHECK(hipMemcpyAsync(d_off, h_off.data(), cells * sizeof(uint64_t),
                              hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_partition_emit_vc, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const uint8_t*)bytes->ptr, (const uint32_t*)offsets->ptr, n, tile,
+    hipLaunchKernelGGL(k_partition_emit<P>, dim3(nb), dim3(BLOCK), 0, s->stream, p, n, tile,
                        nch, d_off, (uint32_t*)row_indexes_out->ptr);
     HIP_CHECK(hipStreamSynchronize(s->stream));
-    (void)hipFree(d_hist);
-    (void)hipFree(d_off);
-    free(h_hist);
-    free(h_off);
     return GPUE_OK;
 }
 
+// Async form: hist -> k_partition_scan -> emit on the session stream, no host
+// round trip. scratch holds hist (u32) then offsets (u64) per (block, channel).
+template <class P>
+static int partition_async(gpue_session* s, P p, uint64_t n, uint32_t nch,
+                           gpue_dbuf* row_indexes_out, gpue_dbuf* scratch) {
+    ARG_CHECK(nch >= 1 && nch <= MAX_CH);
+    ARG_CHECK(row_indexes_out->bytes >= n * 4);
+    uint32_t nb = grid_for(n);
+    uint64_t tile = (n + nb - 1) / nb;
+    ARG_CHECK(scratch->bytes >= (uint64_t)nb * nch * 12);
+    uint32_t* d_hist = (uint32_t*)scratch->ptr;
+    uint64_t* d_off = (uint64_t*)((uint8_t*)scratch->ptr + (uint64_t)nb * nch * 4);
+    hipLaunchKernelGGL(k_partition_hist<P>, dim3(nb), dim3(BLOCK), 0, s->stream, p, n, tile,
+                       nch, d_hist);
+    hipLaunchKernelGGL(k_partition_scan, dim3(1), dim3(64), 0, s->stream, d_hist, nb, nch,
+                       d_off);
+    hipLaunchKernelGGL(k_partition_emit<P>, dim3(nb), dim3(BLOCK), 0, s->stream, p, n, tile,
+                       nch, d_off, (uint32_t*)row_indexes_out->ptr);
+    HIP_CHECK(hipGetLastError());
+    return GPUE_OK;
+}
 
-extern "C" int gpue_partition_2xi32(gpue_session* s, gpue_dbuf* a, gpue_dbuf* b,
-                                    uint64_t n, uint32_t nch, uint64_t* start_points_out,
-                                    gpue_dbuf* row_indexes_out);
+// the three u32-key sync entries differ only in HV
+template <int HV>
+static int partition_u32_sync(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
+                              uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
+    ARG_CHECK(s && keys && start_points_out && row_indexes_out);
+    ARG_CHECK(keys->bytes >= n * 4);
+    return partition_sync(s, PartU32<HV>{(const uint32_t*)keys->ptr}, n, nch,
+                          start_points_out, row_indexes_out);
+}
+
+int gpue_partition_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
+                       uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
+    return partition_u32_sync<0>(s, keys, n, nch, start_points_out, row_indexes_out);
+}
+
+// version-1 exchange hash (xxh3) partition — exchange_sink_operator.cpp:
+// 604-610's `_exchange_hash_function_version == 1` branch
+int gpue_partition_xxh3_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
+                            uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
+    return partition_u32_sync<1>(s, keys, n, nch, start_points_out, row_indexes_out);
+}
+
+// bucket-shuffle hash path (zlib crc32, seed 0) — the third exchange hash
+// (exchange_sink_operator.cpp:617-622)
+int gpue_partition_crc_i32(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
+                           uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
+    return partition_u32_sync<2>(s, keys, n, nch, start_points_out, row_indexes_out);
+}
+
+int gpue_partition_i32_async(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
+                             gpue_dbuf* row_indexes_out, gpue_dbuf* scratch) {
+    ARG_CHECK(s && keys && row_indexes_out && scratch);
+    ARG_CHECK(keys->bytes >= n * 4);
+    return partition_async(s, PartU32<0>{(const uint32_t*)keys->ptr}, n, nch, row_indexes_out,
+                           scratch);
+}
+
+int gpue_partition_i64(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
+                       uint64_t* start_points_out, gpue_dbuf* row_indexes_out) {
+    ARG_CHECK(s && keys && start_points_out && row_indexes_out);
+    ARG_CHECK(keys->bytes >= n * 8);
+    return partition_sync(s, PartU64{(const uint64_t*)keys->ptr}, n, nch, start_points_out,
+                          row_indexes_out);
+}
+
+int gpue_partition_i64_async(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t nch,
+                             gpue_dbuf* row_indexes_out, gpue_dbuf* scratch) {
+    ARG_CHECK(s && keys && row_indexes_out && scratch);
+    ARG_CHECK(keys->bytes >= n * 8);
+    return partition_async(s, PartU64{(const uint64_t*)keys->ptr}, n, nch, row_indexes_out,
+                           scratch);
+}
+
 int gpue_partition_2xi32(gpue_session* s, gpue_dbuf* a, gpue_dbuf* b, uint64_t n,
                          uint32_t nch, uint64_t* start_points_out,
                          gpue_dbuf* row_indexes_out) {
     ARG_CHECK(s && a && b && start_points_out && row_indexes_out);
-    ARG_CHECK(nch >= 1 && nch <= MAX_CH);
-    ARG_CHECK(a->bytes >= n * 4 && b->bytes >= n * 4 && row_indexes_out->bytes >= n * 4);
-    uint32_t nb = grid_for(n);
-    uint64_t tile = (n + nb - 1) / nb;
-    uint32_t* d_hist = nullptr;
-    uint64_t* d_off = nullptr;
-    HIP_CHECK(hipMalloc(&d_hist, (uint64_t)nb * nch * sizeof(uint32_t)));
-    hipLaunchKernelGGL(k_partition_hist_2xi32, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const int32_t*)a->ptr, (const int32_t*)b->ptr, n, tile, nch, d_hist);
-    uint32_t* h_hist = (uint32_t*)malloc((uint64_t)nb * nch * sizeof(uint32_t));
-    uint64_t* h_off = (uint64_t*)malloc((uint64_t)nb * nch * sizeof(uint64_t));
-    HIP_CHECK(hipMemcpyAsync(h_hist, d_hist, (uint64_t)nb * nch * sizeof(uint32_t),
-                             hipMemcpyDeviceToHost, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    uint64_t acc = 0;
-    for (uint32_t c = 0; c < nch; c++) {
-        start_points_out[c] = acc;
-        for (uint32_t blk = 0; blk < nb; blk++) {
-            h_off[(uint64_t)blk * nch + c] = acc;
-            acc += h_hist[(uint64_t)blk * nch + c];
-        }
-    }
-    start_points_out[nch] = acc;
-    HIP_CHECK(hipMalloc(&d_off, (uint64_t)nb * nch * sizeof(uint64_t)));
-    HIP_CHECK(hipMemcpyAsync(d_off, h_off, (uint64_t)nb * nch * sizeof(uint64_t),
-                             hipMemcpyHostToDevice, s->stream));
-    hipLaunchKernelGGL(k_partition_emit_2xi32, dim3(nb), dim3(BLOCK), 0, s->stream,
-                       (const int32_t*)a->ptr, (const int32_t*)b->ptr, n, tile, nch, d_off,
-                       (uint32_t*)row_indexes_out->ptr);
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    (void)hipFree(d_hist);
-    (void)hipFree(d_off);
-    free(h_hist);
-    free(h_off);
-    return GPUE_OK;
+    ARG_CHECK(a->bytes >= n * 4 && b->bytes >= n * 4);
+    return partition_sync(s, Part2xI32{(const int32_t*)a->ptr, (const int32_t*)b->ptr}, n,
+                          nch, start_points_out, row_indexes_out);
+}
+
+int gpue_partition_varchar(gpue_session* s, gpue_dbuf* bytes, gpue_dbuf* offsets,
+                           uint64_t n, uint32_t nch, uint64_t* start_points_out,
+                           gpue_dbuf* row_indexes_out) {
+    ARG_CHECK(s && bytes && offsets && start_points_out && row_indexes_out);
+    ARG_CHECK(offsets->bytes >= (n + 1) * 4);
+    return partition_sync(s, PartVarchar{(const uint8_t*)bytes->ptr,
+                                         (const uint32_t*)offsets->ptr}, n, nch,
+                          start_points_out, row_indexes_out);
 }
 
 // ---------------------------------------------------------------------------
@@ -8226,22 +7942,6 @@ int gpue_q3_probe_agg(gpue_session* s, gpue_dbuf* lk, gpue_dbuf* ext, gpue_dbuf*
 // (reference exchange_sink_operator.cpp:670: per-channel row slices are
 // materialized by gathering source rows at the counting-sorted indexes)
 // ---------------------------------------------------------------------------
-__global__ void k_gather_u32(const uint32_t* __restrict__ in,
-                             const uint32_t* __restrict__ idx, uint64_t n,
-                             uint32_t* __restrict__ out) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        out[i] = in[idx[i]];
-}
-
-__global__ void k_gather_u64(const uint64_t* __restrict__ in,
-                             const uint32_t* __restrict__ idx, uint64_t n,
-                             uint64_t* __restrict__ out) {
-    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        out[i] = in[idx[i]];
-}
-
 extern "C" int gpue_gather_u64(gpue_session* s, gpue_dbuf* in, gpue_dbuf* idx, uint64_t n,
                                gpue_dbuf* out);
 int gpue_gather_u64(gpue_session* s, gpue_dbuf* in, gpue_dbuf* idx, uint64_t n,
