@@ -224,6 +224,116 @@ int gpue_mask_compact(gpue_session* s, gpue_dbuf* mask, uint64_t n_rows,
                       gpue_dbuf* out_row_idx /* nullable; u32 surviving row indices, ascending */,
                       uint64_t* out_count);
 
+/* ---- scalar expressions ----
+ * The Project step: ExprContext::evaluate over arithmetic, cast and
+ * conditional expressions (reference be/src/exprs/arithmetic_expr.cpp,
+ * cast_expr.cpp, condition_expr.cpp), run between scan/filter and join/agg.
+ * ONE pass over the input columns evaluates up to GPUE_EXPR_MAX_OUT
+ * expressions and writes every output column. Same machine as the predicate
+ * section with a value stack in place of the truth stack; no existing entry
+ * changes.
+ *
+ * The program is postfix over parallel arrays (op, col, a): at most
+ * GPUE_EXPR_MAX_INSNS instructions, stack depth at most GPUE_EXPR_MAX_STACK.
+ * Every stack value is an int64 plus a NULL flag. I32 columns are
+ * sign-extended on load; a row is NULL iff its in_nulls byte is nonzero, and
+ * the value stored under an input NULL row is never read into a result.
+ *
+ * Leaves: X_COL pushes input column `col`, X_CONST pushes `a`, X_NULL the
+ * NULL literal. Unary: X_NEG, X_ABS (two's-complement wrapping:
+ * ABS(INT64_MIN) = INT64_MIN), X_NOT (1 if the value is 0, else 0),
+ * X_IS_NULL (1 or 0, never NULL), X_CAST_I32 (a value outside the int32 range
+ * becomes NULL, the reference's cast-overflow result). Binary, left operand
+ * pushed first: X_ADD / X_SUB / X_MUL wrap; X_DIV truncates toward zero, a
+ * zero divisor gives NULL, INT64_MIN / -1 gives INT64_MIN; X_MOD takes the
+ * sign of the dividend, a zero divisor gives NULL, x % -1 gives 0.
+ * GPUE_X_CHECKED OR-ed into ADD, SUB, MUL, NEG or ABS turns signed overflow
+ * into NULL — the decimal64 overflow-to-NULL mode (decimals are scaled int64;
+ * the caller owns the scale). NULL in gives NULL out for all of these.
+ * X_EQ..X_GE compare two stack values, signed: 1 or 0, NULL if either side
+ * is NULL. X_AND / X_OR are Kleene as in the predicate section, over nonzero
+ * = TRUE, zero = FALSE; the result is 1, 0 or NULL. X_IF pops else, then,
+ * cond and yields `then` iff cond is non-NULL and nonzero, otherwise `else`
+ * (CASE WHEN chains lower to nested IF; a missing ELSE is X_NULL). X_IFNULL
+ * pops b, a and yields a unless it is NULL, otherwise b. X_OUT pops the top
+ * of the stack into output `col`; the stack must be empty after each X_OUT,
+ * every output index in [0, n_out) is written exactly once, and the program
+ * ends with an X_OUT.
+ *
+ * Outputs: XO_I64 stores the value, XO_I32 its low 32 bits (a checked
+ * narrowing is X_CAST_I32), XO_MASK a bitmap in exactly gpue_pred_eval_mask's
+ * format — a row's bit is set iff the value is non-NULL and nonzero, trailing
+ * bits of the last word are 0 — which feeds gpue_mask_compact directly. The
+ * value stored under a NULL row is 0 and out_nulls[k][row] is 1 or 0, so
+ * whole buffers compare bit-exactly. out_nulls[k] of an XO_MASK output is
+ * ignored.
+ *
+ * Static nullability, computed on the host while validating: X_COL is
+ * nullable iff the column has a null mask; X_NULL, DIV, MOD, CAST_I32 and
+ * checked ops are nullable; IS_NULL is not; IFNULL is nullable iff b is; IF
+ * iff then or else is; every other op iff any operand is.
+ *
+ * GPUE_ERR_ARG, before any launch or allocation, for: n_insns outside
+ * 1..GPUE_EXPR_MAX_INSNS, n_out outside 1..GPUE_EXPR_MAX_OUT, n_in_cols
+ * outside 0..GPUE_EXPR_MAX_IN_COLS; an unknown op or flag, or CHECKED on an
+ * op that does not take it; stack underflow, depth above GPUE_EXPR_MAX_STACK,
+ * or a non-empty stack after an OUT; a program that does not end with an OUT;
+ * an output written twice or never; a column or output index out of range; an
+ * unknown in_type / out_type; a nullable expression whose out_nulls[k] is
+ * NULL (XO_MASK outputs excepted); n_rows >= 2^32; any buffer shorter than
+ * n_rows elements (a mask: ceil(n_rows/64)*8 bytes); any output or out_null
+ * that overlaps an input, an input null or another output / out_null.
+ * n_rows == 0 returns GPUE_OK. */
+/* leaves */
+#define GPUE_X_COL 32
+#define GPUE_X_CONST 33
+#define GPUE_X_NULL 34
+/* unary */
+#define GPUE_X_NEG 40
+#define GPUE_X_ABS 41
+#define GPUE_X_NOT 42
+#define GPUE_X_IS_NULL 43
+#define GPUE_X_CAST_I32 44
+/* binary arithmetic */
+#define GPUE_X_ADD 48
+#define GPUE_X_SUB 49
+#define GPUE_X_MUL 50
+#define GPUE_X_DIV 51
+#define GPUE_X_MOD 52
+/* comparisons */
+#define GPUE_X_EQ 56
+#define GPUE_X_NE 57
+#define GPUE_X_LT 58
+#define GPUE_X_LE 59
+#define GPUE_X_GT 60
+#define GPUE_X_GE 61
+/* logic, select, output */
+#define GPUE_X_AND 64
+#define GPUE_X_OR 65
+#define GPUE_X_IF 66
+#define GPUE_X_IFNULL 67
+#define GPUE_X_OUT 68
+/* OR-ed into ADD / SUB / MUL / NEG / ABS: signed overflow -> NULL */
+#define GPUE_X_CHECKED 0x200
+/* output types */
+#define GPUE_XO_I32 0
+#define GPUE_XO_I64 1
+#define GPUE_XO_MASK 2
+#define GPUE_EXPR_MAX_INSNS 64
+#define GPUE_EXPR_MAX_STACK 8
+#define GPUE_EXPR_MAX_OUT 8
+#define GPUE_EXPR_MAX_IN_COLS 64
+int gpue_expr_project(gpue_session* s,
+                      gpue_dbuf** in_cols,
+                      gpue_dbuf** in_nulls, /* may be NULL; entries may be NULL; u8, nonzero = NULL row */
+                      const int32_t* in_type /* GPUE_PT_I32 / GPUE_PT_I64 */, int n_in_cols,
+                      const int32_t* insn_op, const int32_t* insn_col,
+                      const int64_t* insn_a, int n_insns,
+                      gpue_dbuf** out_cols,
+                      gpue_dbuf** out_nulls, /* may be NULL; entries may be NULL; u8, 1 = NULL row */
+                      const int32_t* out_type /* GPUE_XO_I32 / GPUE_XO_I64 / GPUE_XO_MASK */,
+                      int n_out, uint64_t n_rows);
+
 /* ---- hash-join build ----
  * Replaces JoinHashTable::build with the RANGE_DIRECT_MAPPING method the
  * selector takes for dense int keys (reference

@@ -3220,6 +3220,410 @@ int gpue_mask_compact(gpue_session* s, gpue_dbuf* mask, uint64_t n_rows, gpue_db
 }
 
 // ---------------------------------------------------------------------------
+// Scalar expressions: a postfix arithmetic / cast / CASE program -> up to
+// GPUE_EXPR_MAX_OUT output columns in one pass (gpue_expr_project).
+// DESIGN.md §4f; measured: §4b rows "expr_project".
+//
+// The predicate machine above with a value stack: same wave-coalesced layout
+// (a wave owns EXPR_STEPS contiguous 64-row steps, so every load and store is
+// a coalesced run and a MASK output's word is the step's __ballot), same
+// by-value program in the kernel-argument segment (ExprProgram, ~2 KB), so
+// decode is scalar loads + wave-uniform branches. The stack is
+// GPUE_EXPR_MAX_STACK statically indexed int64 registers per step moved as a
+// shift register (slot 0 = top: push shifts down, pop shifts up) plus one u32
+// of NULL flags shifted alongside — never a runtime-indexed array, which
+// would go to scratch (the recorded negative at k_filter_lookback_pipe).
+// ---------------------------------------------------------------------------
+// 2 steps: in the 8-slot instance 2 x 8 x 64-bit stack slots = 32 VGPRs of
+// stack, 72 VGPRs in all — the most that still gives 7 waves/SIMD — and no
+// scratch; the 4-slot instance has 43 VGPRs and 8 waves.
+// Measured against it at 100 M rows: 1 step (44 VGPRs) 10 % slower; loading
+// the first 2 or 4 columns ahead of the program (92 / 107 VGPRs, 5 / 4 waves)
+// 30-55 % slower on a * b, and 2.3x slower at 4 steps (197 VGPRs).
+static constexpr int EXPR_STEPS = 2;                               // 64-row steps per wave run
+// 7 waves/SIMD is 1792 resident blocks: at the engine-wide 2048 cap the last
+// 256 blocks start only when the first finish and a call takes two rounds
+// (a * b over 100 M rows: 0.765 ms at 2048, 0.579 at 16384, 0.571 at 65536,
+// 0.569 uncapped). 16384 takes nearly all of it and keeps the strided path
+// reachable by a test of 8.4 M rows.
+static constexpr uint64_t EXPR_MAX_GRID = 16384;
+static constexpr int EXPR_WAVE_RUN = WAVE * EXPR_STEPS;            // 128 rows
+static constexpr int EXPR_TILE = EXPR_WAVE_RUN * (BLOCK / WAVE);   // 512 rows
+// a valid program has at most GPUE_EXPR_MAX_INSNS - 1 leaves
+static constexpr int EXPR_MAX_SLOTS = GPUE_EXPR_MAX_INSNS;
+static constexpr int EXPR_STACK = GPUE_EXPR_MAX_STACK;
+
+// meta: bits 0-7 op, 8 CHECKED, 9 column is I64, 16-23 input slot / output index
+struct ExprProgram {
+    const void* col[EXPR_MAX_SLOTS];
+    const uint8_t* nul[EXPR_MAX_SLOTS];
+    int64_t a[GPUE_EXPR_MAX_INSNS];
+    uint32_t meta[GPUE_EXPR_MAX_INSNS];
+    void* out[GPUE_EXPR_MAX_OUT];
+    uint8_t* out_nul[GPUE_EXPR_MAX_OUT];
+    int32_t out_type[GPUE_EXPR_MAX_OUT];
+    int n_insns;
+};
+
+// One step's stack of D slots. Every index below is a compile-time constant
+// after unrolling, so v[] lives in registers. D is 4 when the program's deepest
+// point fits (the host knows it from validating), else 8, so a shallow program
+// does not pay to shift slots it never fills. (A 2-slot instance was built
+// too: the compiler put 64 B/lane of it in scratch, so it is not used.)
+template <int D>
+struct ExprStack {
+    int64_t v[D];
+    uint32_t nb; // bit k = slot k is NULL
+
+    __device__ __forceinline__ void push(int64_t x, bool isn) {
+        #pragma unroll
+        for (int k = D - 1; k > 0; k--) v[k] = v[k - 1];
+        v[0] = x;
+        nb = (nb << 1) | (uint32_t)isn;
+    }
+    // replace the top POP values by one
+    template <int POP>
+    __device__ __forceinline__ void fold(int64_t x, bool isn) {
+        #pragma unroll
+        for (int k = 1; k + POP - 1 < D; k++) v[k] = v[k + POP - 1];
+        v[0] = x;
+        nb = ((nb >> POP) << 1) | (uint32_t)isn;
+    }
+};
+
+__device__ static __forceinline__ int64_t expr_wrap_neg(int64_t x) {
+    return (int64_t)(0ull - (uint64_t)x);
+}
+
+__device__ static __forceinline__ void
+expr_unary(uint32_t op, bool chk, int64_t x, bool xn, int64_t& r, bool& rn) {
+    rn = xn;
+    switch (op) {
+    case GPUE_X_NEG:
+        r = expr_wrap_neg(x);
+        if (chk) rn = rn || x == INT64_MIN;
+        break;
+    case GPUE_X_ABS:
+        r = x < 0 ? expr_wrap_neg(x) : x;
+        if (chk) rn = rn || x == INT64_MIN;
+        break;
+    case GPUE_X_NOT: r = x == 0; break;
+    case GPUE_X_IS_NULL:
+        r = xn;
+        rn = false;
+        break;
+    default: /* GPUE_X_CAST_I32 */
+        r = x;
+        rn = rn || x != (int64_t)(int32_t)x;
+        break;
+    }
+}
+
+// x was pushed first (left operand), y second
+__device__ static __forceinline__ void
+expr_binary(uint32_t op, bool chk, int64_t x, bool xn, int64_t y, bool yn, int64_t& r,
+            bool& rn) {
+    rn = xn || yn;
+    switch (op) {
+    case GPUE_X_ADD:
+        r = (int64_t)((uint64_t)x + (uint64_t)y);
+        if (chk) rn = rn || ((x ^ r) & (y ^ r)) < 0;
+        break;
+    case GPUE_X_SUB:
+        r = (int64_t)((uint64_t)x - (uint64_t)y);
+        if (chk) rn = rn || ((x ^ y) & (x ^ r)) < 0;
+        break;
+    case GPUE_X_MUL:
+        r = (int64_t)((uint64_t)x * (uint64_t)y);
+        if (chk) rn = rn || __mul64hi(x, y) != (r >> 63);
+        break;
+    case GPUE_X_DIV:
+    case GPUE_X_MOD: {
+        // the divisor a lane divides by is never 0 and never -1: 1 stands in
+        // where it is 0 or NULL (result NULL) and where it is -1 (handled
+        // below), so no lane executes an undefined division
+        rn = rn || y == 0;
+        const bool m1 = y == -1;
+        const int64_t d = (rn || m1) ? 1 : y;
+        const int64_t q = x / d;
+        if (op == GPUE_X_DIV) r = m1 ? expr_wrap_neg(x) : q; // INT64_MIN / -1 = INT64_MIN
+        else r = m1 ? 0 : x - q * d;                          // sign of the dividend
+        break;
+    }
+    case GPUE_X_EQ: r = x == y; break;
+    case GPUE_X_NE: r = x != y; break;
+    case GPUE_X_LT: r = x < y; break;
+    case GPUE_X_LE: r = x <= y; break;
+    case GPUE_X_GT: r = x > y; break;
+    case GPUE_X_GE: r = x >= y; break;
+    default: { /* GPUE_X_AND / GPUE_X_OR, Kleene */
+        const bool xt = !xn && x != 0, xf = !xn && x == 0;
+        const bool yt = !yn && y != 0, yf = !yn && y == 0;
+        const bool rt = op == GPUE_X_AND ? (xt && yt) : (xt || yt);
+        const bool rf = op == GPUE_X_AND ? (xf || yf) : (xf && yf);
+        r = rt;
+        rn = !(rt || rf);
+        break;
+    }
+    }
+}
+
+// One wave run: EXPR_STEPS 64-row steps from row `base`. FULL = the whole run
+// lies below n, so nothing is predicated; in the ragged form a lane at or
+// beyond n never loads or stores (it computes on zeros).
+template <bool FULL, int D>
+__device__ static __forceinline__ void
+expr_run(const ExprProgram& p, uint64_t base, uint64_t n, int lane) {
+    ExprStack<D> st[EXPR_STEPS];
+    bool act[EXPR_STEPS];
+    const uint64_t row0 = base + lane;
+    #pragma unroll
+    for (int j = 0; j < EXPR_STEPS; j++) {
+        #pragma unroll
+        for (int k = 0; k < D; k++) st[j].v[k] = 0;
+        st[j].nb = 0;
+        act[j] = FULL || row0 + (uint64_t)j * WAVE < n;
+    }
+    for (int i = 0; i < p.n_insns; i++) {
+        const uint32_t m = p.meta[i];
+        const uint32_t op = m & 0xffu;
+        const bool chk = (m >> 8) & 1u;
+        const uint32_t idx = (m >> 16) & 0xffu;
+        if (op == GPUE_X_COL) {
+            // all steps' loads issue before the first push
+            const bool is64 = (m >> 9) & 1u;
+            const void* c0 = p.col[idx];
+            const uint8_t* n0 = p.nul[idx];
+            int64_t x[EXPR_STEPS];
+            bool isn[EXPR_STEPS];
+            #pragma unroll
+            for (int j = 0; j < EXPR_STEPS; j++) {
+                const uint64_t row = row0 + (uint64_t)j * WAVE;
+                x[j] = 0;
+                isn[j] = false;
+                if (act[j]) {
+                    if (n0) isn[j] = n0[row] != 0;
+                    x[j] = is64 ? ((const int64_t*)c0)[row] : (int64_t)((const int32_t*)c0)[row];
+                }
+            }
+            #pragma unroll
+            for (int j = 0; j < EXPR_STEPS; j++) st[j].push(x[j], isn[j]);
+        } else if (op == GPUE_X_CONST || op == GPUE_X_NULL) {
+            const int64_t a = p.a[i];
+            #pragma unroll
+            for (int j = 0; j < EXPR_STEPS; j++) st[j].push(a, op == GPUE_X_NULL);
+        } else if (op < GPUE_X_ADD) { // unary
+            #pragma unroll
+            for (int j = 0; j < EXPR_STEPS; j++) {
+                int64_t r;
+                bool rn;
+                expr_unary(op, chk, st[j].v[0], st[j].nb & 1u, r, rn);
+                st[j].template fold<1>(r, rn);
+            }
+        } else if (op < GPUE_X_IF) { // binary arithmetic, compare, AND / OR
+            #pragma unroll
+            for (int j = 0; j < EXPR_STEPS; j++) {
+                int64_t r;
+                bool rn;
+                expr_binary(op, chk, st[j].v[1], (st[j].nb >> 1) & 1u, st[j].v[0],
+                            st[j].nb & 1u, r, rn);
+                st[j].template fold<2>(r, rn);
+            }
+        } else if (op == GPUE_X_IF) { // slot 0 else, 1 then, 2 cond
+            if constexpr (D >= 3) { // v[2]: a program with an IF is at least 3 deep
+                #pragma unroll
+                for (int j = 0; j < EXPR_STEPS; j++) {
+                    const uint32_t nb = st[j].nb;
+                    const bool take = !((nb >> 2) & 1u) && st[j].v[2] != 0;
+                    st[j].template fold<3>(take ? st[j].v[1] : st[j].v[0],
+                                           ((take ? nb >> 1 : nb) & 1u) != 0);
+                }
+            }
+        } else if (op == GPUE_X_IFNULL) { // slot 0 b, 1 a
+            #pragma unroll
+            for (int j = 0; j < EXPR_STEPS; j++) {
+                const uint32_t nb = st[j].nb;
+                const bool an = (nb >> 1) & 1u;
+                st[j].template fold<2>(an ? st[j].v[0] : st[j].v[1], an && (nb & 1u));
+            }
+        } else { // GPUE_X_OUT: the stack is empty afterwards (validated on the host)
+            const int32_t ot = p.out_type[idx];
+            void* o = p.out[idx];
+            uint8_t* on = p.out_nul[idx];
+            #pragma unroll
+            for (int j = 0; j < EXPR_STEPS; j++) {
+                const uint64_t row = row0 + (uint64_t)j * WAVE;
+                const bool isn = st[j].nb & 1u;
+                const int64_t x = isn ? 0 : st[j].v[0];
+                if (ot == GPUE_XO_MASK) {
+                    // the step's ballot is its mask word; inactive lanes vote 0,
+                    // so the last word's trailing bits are 0
+                    const uint64_t word = __ballot(act[j] && x != 0);
+                    if (lane == 0 && (FULL || base + (uint64_t)j * WAVE < n))
+                        ((uint64_t*)o)[(base >> 6) + j] = word;
+                } else if (act[j]) {
+                    if (ot == GPUE_XO_I64) ((int64_t*)o)[row] = x;
+                    else ((int32_t*)o)[row] = (int32_t)x;
+                    if (on) on[row] = (uint8_t)isn;
+                }
+                st[j].nb = 0;
+            }
+        }
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(BLOCK) void
+k_expr_project(const ExprProgram p, uint64_t n, uint64_t n_tiles) {
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t base = t * EXPR_TILE + (uint64_t)wid * EXPR_WAVE_RUN;
+        if (base >= n) continue; // wave-uniform
+        if (base + EXPR_WAVE_RUN <= n) expr_run<true, D>(p, base, n, lane);
+        else expr_run<false, D>(p, base, n, lane);
+    }
+}
+
+int gpue_expr_project(gpue_session* s, gpue_dbuf** in_cols, gpue_dbuf** in_nulls,
+                      const int32_t* in_type, int n_in_cols, const int32_t* insn_op,
+                      const int32_t* insn_col, const int64_t* insn_a, int n_insns,
+                      gpue_dbuf** out_cols, gpue_dbuf** out_nulls, const int32_t* out_type,
+                      int n_out, uint64_t n_rows) {
+    ARG_CHECK(s && insn_op && insn_col && insn_a && out_cols && out_type);
+    ARG_CHECK(n_in_cols >= 0 && n_in_cols <= GPUE_EXPR_MAX_IN_COLS);
+    ARG_CHECK(n_in_cols == 0 || (in_cols && in_type));
+    ARG_CHECK(n_insns >= 1 && n_insns <= GPUE_EXPR_MAX_INSNS);
+    ARG_CHECK(n_out >= 1 && n_out <= GPUE_EXPR_MAX_OUT);
+    ARG_CHECK(n_rows < (1ull << 32));
+    const uint64_t n_words = (n_rows + 63) >> 6;
+    auto in_null = [&](int c) { return in_nulls ? in_nulls[c] : nullptr; };
+    auto out_null = [&](int k) {
+        return out_nulls && out_type[k] != GPUE_XO_MASK ? out_nulls[k] : nullptr;
+    };
+    for (int c = 0; c < n_in_cols; c++) {
+        ARG_CHECK(in_type[c] == GPUE_PT_I32 || in_type[c] == GPUE_PT_I64);
+        ARG_CHECK(in_cols[c] != nullptr);
+        ARG_CHECK(in_cols[c]->bytes >= n_rows * (in_type[c] == GPUE_PT_I64 ? 8 : 4));
+        if (in_null(c)) ARG_CHECK(in_null(c)->bytes >= n_rows);
+    }
+    for (int k = 0; k < n_out; k++) {
+        ARG_CHECK(out_type[k] == GPUE_XO_I32 || out_type[k] == GPUE_XO_I64 ||
+                  out_type[k] == GPUE_XO_MASK);
+        ARG_CHECK(out_cols[k] != nullptr);
+        ARG_CHECK(out_cols[k]->bytes >= (out_type[k] == GPUE_XO_MASK ? n_words * 8
+                                         : n_rows * (out_type[k] == GPUE_XO_I64 ? 8 : 4)));
+        if (out_null(k)) ARG_CHECK(out_null(k)->bytes >= n_rows);
+    }
+    // every buffer the kernel writes, against every buffer of the call
+    auto overlap = [](const gpue_dbuf* x, const gpue_dbuf* y) {
+        const char *xa = (const char*)x->ptr, *ya = (const char*)y->ptr;
+        return xa < ya + y->bytes && ya < xa + x->bytes;
+    };
+    const gpue_dbuf* wr[2 * GPUE_EXPR_MAX_OUT];
+    int n_wr = 0;
+    for (int k = 0; k < n_out; k++) {
+        wr[n_wr++] = out_cols[k];
+        if (out_null(k)) wr[n_wr++] = out_null(k);
+    }
+    for (int x = 0; x < n_wr; x++) {
+        for (int c = 0; c < n_in_cols; c++) {
+            ARG_CHECK(!overlap(wr[x], in_cols[c]));
+            if (in_null(c)) ARG_CHECK(!overlap(wr[x], in_null(c)));
+        }
+        for (int y = x + 1; y < n_wr; y++) ARG_CHECK(!overlap(wr[x], wr[y]));
+    }
+    // ---- validate the program and lower it to ExprProgram (host only) ----
+    ExprProgram p;
+    memset(&p, 0, sizeof(p));
+    p.n_insns = n_insns;
+    int slot_col[EXPR_MAX_SLOTS];
+    int n_slots = 0;
+    auto slot_of = [&](int c) -> int {
+        for (int k = 0; k < n_slots; k++)
+            if (slot_col[k] == c) return k;
+        if (n_slots == EXPR_MAX_SLOTS) return -1;
+        slot_col[n_slots] = c;
+        p.col[n_slots] = in_cols[c]->ptr;
+        p.nul[n_slots] = in_null(c) ? (const uint8_t*)in_null(c)->ptr : nullptr;
+        return n_slots++;
+    };
+    bool nullable[GPUE_EXPR_MAX_STACK]; // static nullability of each stack slot, [depth-1] = top
+    bool written[GPUE_EXPR_MAX_OUT] = {false};
+    int depth = 0, max_depth = 0;
+    for (int i = 0; i < n_insns; i++) {
+        const int32_t raw = insn_op[i];
+        const int32_t op = raw & ~GPUE_X_CHECKED;
+        const bool chk = (raw & GPUE_X_CHECKED) != 0;
+        ARG_CHECK(!chk || op == GPUE_X_ADD || op == GPUE_X_SUB || op == GPUE_X_MUL ||
+                  op == GPUE_X_NEG || op == GPUE_X_ABS);
+        uint32_t idx = 0, is64 = 0;
+        if (op >= GPUE_X_COL && op <= GPUE_X_NULL) { // leaves
+            ARG_CHECK(depth < GPUE_EXPR_MAX_STACK); // stack overflow
+            bool nl = op == GPUE_X_NULL;
+            if (op == GPUE_X_COL) {
+                const int32_t c = insn_col[i];
+                ARG_CHECK(c >= 0 && c < n_in_cols);
+                const int sl = slot_of(c);
+                ARG_CHECK(sl >= 0);
+                idx = (uint32_t)sl;
+                is64 = in_type[c] == GPUE_PT_I64;
+                nl = in_null(c) != nullptr;
+            } else if (op == GPUE_X_CONST) {
+                p.a[i] = insn_a[i];
+            }
+            nullable[depth++] = nl;
+            max_depth = std::max(max_depth, depth);
+        } else if (op >= GPUE_X_NEG && op <= GPUE_X_CAST_I32) { // unary
+            ARG_CHECK(depth >= 1); // stack underflow
+            bool& t = nullable[depth - 1];
+            if (op == GPUE_X_IS_NULL) t = false;
+            else if (op == GPUE_X_CAST_I32 || chk) t = true;
+        } else if ((op >= GPUE_X_ADD && op <= GPUE_X_MOD) ||
+                   (op >= GPUE_X_EQ && op <= GPUE_X_GE) || op == GPUE_X_AND ||
+                   op == GPUE_X_OR || op == GPUE_X_IFNULL) { // binary
+            ARG_CHECK(depth >= 2);
+            const bool xn = nullable[depth - 2], yn = nullable[depth - 1];
+            depth--;
+            nullable[depth - 1] = op == GPUE_X_IFNULL ? yn
+                                  : (xn || yn || chk || op == GPUE_X_DIV || op == GPUE_X_MOD);
+        } else if (op == GPUE_X_IF) {
+            ARG_CHECK(depth >= 3);
+            const bool tn = nullable[depth - 2], en = nullable[depth - 1];
+            depth -= 2;
+            nullable[depth - 1] = tn || en;
+        } else {
+            ARG_CHECK(op == GPUE_X_OUT); // unknown op or flag
+            ARG_CHECK(depth == 1);       // underflow, or values left under the output
+            const int32_t k = insn_col[i];
+            ARG_CHECK(k >= 0 && k < n_out);
+            ARG_CHECK(!written[k]); // output written twice
+            written[k] = true;
+            // a nullable expression needs somewhere to put its NULL flags
+            ARG_CHECK(!nullable[0] || out_type[k] == GPUE_XO_MASK || out_null(k));
+            idx = (uint32_t)k;
+            depth = 0;
+        }
+        p.meta[i] = (uint32_t)op | (chk ? 1u << 8 : 0u) | (is64 << 9) | (idx << 16);
+    }
+    ARG_CHECK(depth == 0); // the program ends with an OUT
+    for (int k = 0; k < n_out; k++) {
+        ARG_CHECK(written[k]); // output never written
+        p.out[k] = out_cols[k]->ptr;
+        p.out_nul[k] = out_null(k) ? (uint8_t*)out_null(k)->ptr : nullptr;
+        p.out_type[k] = out_type[k];
+    }
+    if (n_rows == 0) return GPUE_OK;
+
+    const uint64_t n_tiles = (n_rows + EXPR_TILE - 1) / EXPR_TILE;
+    const uint32_t nb = (uint32_t)(n_tiles < EXPR_MAX_GRID ? n_tiles : EXPR_MAX_GRID);
+    auto kern = max_depth <= 4 ? k_expr_project<4> : k_expr_project<EXPR_STACK>;
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s->stream, p, n_rows, n_tiles);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GPUE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // SERIALIZED_VARCHAR / Slice keys (the selector's last constructor branch):
 // JoinKeyHash<Slice> = crc_hash_32(bytes, len, 0x811C9DC5) & (bucket_size-1)
 // (join_hash_map_helper.h:57-64; CRC32-C + phmap_mix<4>, bitwise device

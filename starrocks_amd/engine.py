@@ -91,6 +91,10 @@ def _declare(lib):
         "gpue_mask_compact": (c_i32, [c_vp, c_vp, c_u64, ctypes.POINTER(c_vp),
                                       ctypes.POINTER(c_vp), c_vp, c_i32, c_vp,
                                       ctypes.POINTER(c_u64)]),
+        "gpue_expr_project": (c_i32, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp),
+                                      c_vp, c_i32, c_vp, c_vp, c_vp, c_i32,
+                                      ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp,
+                                      c_i32, c_u64]),
         "gpue_scan_filter_i64_lt": (c_i32, [c_vp, c_vp, c_u64, c_i64, c_vp, ctypes.POINTER(c_u64)]),
         "gpue_scan_filter_i64_lt_sp": (c_i32, [c_vp, c_vp, c_u64, c_i64, c_vp, ctypes.POINTER(c_u64)]),
         "gpue_join_build_payload_i32": (c_i32, [c_vp, c_vp, c_vp, c_u64, ctypes.POINTER(c_vp)]),
@@ -459,6 +463,61 @@ class Engine:
         finally:
             mask.free()
         return out, cnt
+
+    # --- scalar expressions (gpue.h "scalar expressions") ---
+    XO_I32, XO_I64, XO_MASK = 0, 1, 2
+
+    def expr_project(self, in_cols, program, n_rows, outs):
+        """Evaluate a compiled expression program (expr.compile_exprs) over
+        in_cols = [(DBuf, nulls DBuf or None, PT_I32 / PT_I64), ...] into
+        outs = [(DBuf, nulls DBuf or None, XO_I32 / XO_I64 / XO_MASK), ...],
+        one pass for all outputs. A nullable expression needs a null buffer;
+        an XO_MASK output is a bitmap in pred_eval_mask's format."""
+        op, col, a = program
+        op = np.ascontiguousarray(op, np.int32)
+        col = np.ascontiguousarray(col, np.int32)
+        a = np.ascontiguousarray(a, np.int64)
+        if not (len(op) == len(col) == len(a)):
+            raise ValueError("program arrays differ in length")
+        nc, no = len(in_cols), len(outs)
+        cols = (c_vp * max(nc, 1))(*[c[0]._h for c in in_cols])
+        nulls = (c_vp * max(nc, 1))(*[c[1]._h if c[1] is not None else None
+                                      for c in in_cols])
+        types = np.array([c[2] for c in in_cols], np.int32)
+        ocols = (c_vp * max(no, 1))(*[o[0]._h for o in outs])
+        onulls = (c_vp * max(no, 1))(*[o[1]._h if o[1] is not None else None
+                                       for o in outs])
+        otypes = np.array([o[2] for o in outs], np.int32)
+        _ck(self._lib, self._lib.gpue_expr_project(
+            self._h, cols, nulls, types.ctypes.data_as(c_vp), nc,
+            op.ctypes.data_as(c_vp), col.ctypes.data_as(c_vp), a.ctypes.data_as(c_vp),
+            len(op), ocols, onulls, otypes.ctypes.data_as(c_vp), no, n_rows))
+
+    def project(self, trees, in_cols, out_types, n_rows):
+        """One-shot Project: compile `trees` (expr.py forms; column i =
+        in_cols[i], as expr_project), allocate exact-size outputs — n_rows * 4
+        or 8 bytes, ceil(n_rows/64) * 8 for XO_MASK, 1 byte when that is 0 —
+        and a u8 null buffer only for outputs whose expression is nullable,
+        then run the one pass. Returns [(values DBuf, nulls DBuf or None), ...];
+        the inputs are left alone."""
+        from starrocks_amd.expr import compile_exprs
+        program, nullable = compile_exprs(trees, [c[2] for c in in_cols],
+                                          [c[1] is not None for c in in_cols], out_types)
+        size = {self.XO_I32: n_rows * 4, self.XO_I64: n_rows * 8,
+                self.XO_MASK: (n_rows + 63) // 64 * 8}
+        bufs = []
+        try:
+            for t, nl in zip(out_types, nullable):
+                bufs.append(self.alloc(max(size[t], 1)))
+                bufs.append(self.alloc(max(n_rows, 1)) if nl and t != self.XO_MASK else None)
+            outs = [(bufs[2 * k], bufs[2 * k + 1], t) for k, t in enumerate(out_types)]
+            self.expr_project(in_cols, program, n_rows, outs)
+        except BaseException:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+            raise
+        return [(v, nl) for v, nl, _ in outs]
 
     # --- JoinHashMapSelector restatement (join_hash_table.cpp:164-344) ---
     JM_NAMES = {0: "DIRECT", 1: "RANGE_DIRECT", 2: "RANGE_DIRECT_SET",

@@ -610,6 +610,84 @@ class FilterOperator(Operator):
         return c
 
 
+class ProjectOperator(Operator):
+    """Project as a pass-through operator — ExprContext::evaluate over
+    arithmetic, cast and conditional expressions between scan / filter and
+    join / agg (starrocks_amd/expr.py forms).
+
+    Chunks are {"n": rows, "cols": [DBuf, ...]}. col_map[i] = (chunk column
+    index, chunk column index of its u8 null mask or None, type 0 int32 / 1
+    int64) binds input column i of the trees, as in FilterOperator. keep lists
+    the chunk columns passed through, in that order; every other input column
+    is freed. The output chunk is the kept columns, then per expression its
+    value column (int32 / int64 per out_types[k], or the selection bitmap for
+    XO_MASK) followed by a width-1 null column iff the expression is nullable
+    (never for XO_MASK). The trees are compiled once, at construction;
+    out_widths gives the byte width of every output chunk column (8 for a
+    bitmap: its u64 words).
+
+    Per pushed chunk: exact-size outputs and one expr_project pass. One chunk
+    in, one chunk out, same n.
+
+    Uses only engine.alloc / expr_project and DBuf.free, so it runs against a
+    numpy stand-in engine without a GPU."""
+
+    def __init__(self, engine, trees, col_map, out_types, keep):
+        super().__init__()
+        from starrocks_amd.expr import XO_I32, XO_I64, XO_MASK, compile_exprs
+        self._e = engine
+        self._map = [(int(c), None if nl is None else int(nl), int(t))
+                     for c, nl, t in col_map]
+        self._keep = [int(k) for k in keep]
+        if len(set(self._keep)) != len(self._keep) or any(k < 0 for k in self._keep):
+            raise ValueError("keep must list distinct chunk column indexes")
+        if any(c < 0 or (nl is not None and nl < 0) for c, nl, _ in self._map):
+            raise ValueError("chunk column indexes must be non-negative")
+        self._out_types = [int(t) for t in out_types]
+        self._program, self.nullable = compile_exprs(
+            trees, [t for _, _, t in self._map], [nl is not None for _, nl, _ in self._map],
+            self._out_types)
+        self._mask_t = XO_MASK
+        self._size = {XO_I32: lambda n: n * 4, XO_I64: lambda n: n * 8,
+                      XO_MASK: lambda n: (n + 63) // 64 * 8}
+        self.out_widths = []
+        for t, nl in zip(self._out_types, self.nullable):
+            self.out_widths.append(4 if t == XO_I32 else 8)
+            if nl and t != XO_MASK:
+                self.out_widths.append(1)
+        self._out = None
+        self.rows = 0
+
+    def need_input(self):
+        return self._out is None and not self._finishing
+
+    def has_output(self):
+        return self._out is not None
+
+    def push_chunk(self, chunk):
+        n, cols = chunk["n"], chunk["cols"]
+        in_cols = [(cols[c], None if nl is None else cols[nl], t) for c, nl, t in self._map]
+        outs = []
+        for t, nl in zip(self._out_types, self.nullable):
+            outs.append((self._e.alloc(max(self._size[t](n), 1)),
+                         self._e.alloc(max(n, 1)) if nl and t != self._mask_t else None, t))
+        self._e.expr_project(in_cols, self._program, n, outs)
+        for k, b in enumerate(cols):
+            if k not in self._keep:
+                b.free()
+        new_cols = [cols[k] for k in self._keep]
+        for v, nl, _ in outs:
+            new_cols.append(v)
+            if nl is not None:
+                new_cols.append(nl)
+        self.rows += n
+        self._out = {"n": n, "cols": new_cols}
+
+    def pull_chunk(self):
+        c, self._out = self._out, None
+        return c
+
+
 def q1_operator_pipeline(engine, seed, total_rows, year=1993,
                          chunk_rows=DEFAULT_CHUNK_ROWS, dim_chunk_rows=1000):
     """Config-2's plan as the reference would run it — dim source -> build
