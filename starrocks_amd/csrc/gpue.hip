@@ -129,6 +129,8 @@ struct gpue_dbuf {
     bool owned = true; // false: wraps external device memory (e.g. a torch tensor)
 };
 
+static constexpr uint32_t NBC = 64; // most distinct payloads a table ranks densely
+
 struct gpue_join_table {
     gpue_session* s = nullptr;
     int64_t min_key = 0, max_key = 0;
@@ -144,6 +146,14 @@ struct gpue_join_table {
     int64_t set_min = 0, set_max = -1; // bounding range of keys with payload != 0
     uint16_t* first16 = nullptr; // 16-bit payload copy when all payloads < 65536:
                                  // halves the random-gather footprint (L2 per XCD is 4 MiB)
+    // dense rank of the payload domain, kept when first16 exists and holds
+    // at most NBC distinct nonzero payloads (null otherwise): lets a
+    // kernel keep one group slot per payload that occurs, not per possible one
+    uint16_t* first16c = nullptr; // rank + 1 of first16[i] in increasing payload
+                                  // order, 0 where first16[i] is 0
+    uint16_t* pay_vals = nullptr; // device, n_pay entries: the payload of each rank
+    uint32_t n_pay = 0;           // distinct nonzero payloads (0: empty pass set)
+    uint32_t pay_max = 0;         // the largest of them
     uint32_t* prefilter = nullptr; // 2^19-bit (64 KB) fold of `bitset` for
                                    // LDS-resident prefiltering (k_q21_star_agg_pf)
     uint32_t* prefilter2w = nullptr; // WIDE split fold (2 x 2^19 bits,
@@ -1691,6 +1701,74 @@ __global__ void k_derive_u16(const uint32_t* __restrict__ first, uint64_t interv
     }
 }
 
+// one bit per nonzero 16-bit payload value that occurs (2048 words, zeroed by
+// the caller); marked per block in LDS first, so that global memory sees one
+// atomic per block and nonzero word, not one per key
+__global__ void k_mark_payloads(const uint16_t* __restrict__ first16, uint64_t interval,
+                                uint32_t* __restrict__ marks) {
+    __shared__ uint32_t m[2048];
+    for (uint32_t w = threadIdx.x; w < 2048; w += blockDim.x) m[w] = 0;
+    __syncthreads();
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < interval; i += stride) {
+        uint32_t v = first16[i];
+        if (v && !((m[v >> 5] >> (v & 31)) & 1u)) atomicOr(&m[v >> 5], 1u << (v & 31));
+    }
+    __syncthreads();
+    for (uint32_t w = threadIdx.x; w < 2048; w += blockDim.x)
+        if (m[w]) atomicOr(&marks[w], m[w]);
+}
+
+// first16c[i] = rank1[first16[i]] (rank1[0] == 0)
+__global__ void k_rank_u16(const uint16_t* __restrict__ first16, uint64_t interval,
+                           const uint8_t* __restrict__ rank1, uint16_t* __restrict__ first16c) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < interval; i += stride)
+        first16c[i] = rank1[first16[i]];
+}
+
+// Dense rank of a payload table's 16-bit payload domain: first16c / pay_vals
+// / n_pay / pay_max when at most NBC distinct nonzero payloads occur, left
+// null otherwise. Synchronises the stream (plan-time work, once per table).
+static int join_table_rank_payloads(gpue_session* s, gpue_join_table* t, uint64_t interval) {
+    DevScratch tmp;
+    uint32_t* d_marks = nullptr;
+    HIP_CHECK(tmp.alloc(&d_marks, 2048 * sizeof(uint32_t)));
+    HIP_CHECK(hipMemsetAsync(d_marks, 0, 2048 * sizeof(uint32_t), s->stream));
+    hipLaunchKernelGGL(k_mark_payloads, dim3(grid_for(interval)), dim3(BLOCK), 0, s->stream,
+                       t->first16, interval, d_marks);
+    std::vector<uint32_t> marks(2048);
+    HIP_CHECK(hipMemcpyAsync(marks.data(), d_marks, 2048 * sizeof(uint32_t),
+                             hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    std::vector<uint8_t> rank1(65536, 0);
+    uint16_t vals[NBC];
+    uint32_t n_pay = 0;
+    for (uint32_t v = 1; v < 65536; v++)
+        if ((marks[v >> 5] >> (v & 31)) & 1u) {
+            if (n_pay == NBC) return GPUE_OK; // too many groups: no compact form
+            vals[n_pay++] = (uint16_t)v;
+            rank1[v] = (uint8_t)n_pay;
+        }
+    uint8_t* d_rank1 = nullptr;
+    HIP_CHECK(tmp.alloc(&d_rank1, rank1.size()));
+    HIP_CHECK(hipMemcpyAsync(d_rank1, rank1.data(), rank1.size(), hipMemcpyHostToDevice,
+                             s->stream));
+    HIP_CHECK(hipMalloc(&t->pay_vals, NBC * sizeof(uint16_t)));
+    HIP_CHECK(hipMemsetAsync(t->pay_vals, 0, NBC * sizeof(uint16_t), s->stream));
+    if (n_pay)
+        HIP_CHECK(hipMemcpyAsync(t->pay_vals, vals, n_pay * sizeof(uint16_t),
+                                 hipMemcpyHostToDevice, s->stream));
+    HIP_CHECK(hipMalloc(&t->first16c, interval * sizeof(uint16_t)));
+    hipLaunchKernelGGL(k_rank_u16, dim3(grid_for(interval)), dim3(BLOCK), 0, s->stream,
+                       t->first16, interval, d_rank1, t->first16c);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s->stream)); // vals / rank1 / tmp leave scope
+    t->n_pay = n_pay;
+    t->pay_max = n_pay ? vals[n_pay - 1] : 0;
+    return GPUE_OK;
+}
+
 __global__ void k_build_range_direct(const int32_t* __restrict__ keys, uint64_t row_count,
                                      int64_t min_key, uint32_t* __restrict__ first,
                                      uint32_t* __restrict__ next) {
@@ -1788,6 +1866,10 @@ int gpue_join_build_payload_i32(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* pay
     HIP_CHECK(hipMemcpyAsync(&ovf, d_ovf, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
     HIP_CHECK(hipStreamSynchronize(s->stream));
     if (ovf) { (void)hipFree(t->first16); t->first16 = nullptr; }
+    if (t->first16) {
+        rc = join_table_rank_payloads(s, t, interval);
+        if (rc != GPUE_OK) return rc;
+    }
     *out = own.release();
     return GPUE_OK;
 }
@@ -1824,6 +1906,8 @@ void gpue_join_table_destroy(gpue_join_table* t) {
     if (t->next) (void)hipFree(t->next);
     if (t->bitset) (void)hipFree(t->bitset);
     if (t->first16) (void)hipFree(t->first16);
+    if (t->first16c) (void)hipFree(t->first16c);
+    if (t->pay_vals) (void)hipFree(t->pay_vals);
     if (t->prefilter) (void)hipFree(t->prefilter);
     if (t->prefilter2) (void)hipFree(t->prefilter2);
     if (t->prefilter2w) (void)hipFree(t->prefilter2w);
@@ -5353,6 +5437,191 @@ k_q21_star_agg_pfq4(const int32_t* __restrict__ pk, const int32_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// Compact-group burst q21 (GPUE_Q21_PF=9): pfq4<., 1>'s stages and bytes with
+// the LDS its 56,000 B group array pins given to a wider fold and a deeper Q1.
+//  groups: g[7 * NBC], indexed (year1-1)*NBC + (rank1-1), where rank1 is the
+//          part table's dense payload rank (first16c, 0 = fails the brand
+//          test, exactly as first16's 0); the end-of-kernel merge adds slot
+//          (y, r) to group_sums[y*1000 + pay_vals[r]-1], so the 7000-slot
+//          output is what the other modes write;
+//  FA:     fold A has 2^FA bits, index idx & (2^FA-1): prefilter2's first half
+//          (18) or prefilter2w's (19); fold B stays prefilter2's hashed 2^18;
+//  K:      the main loop loads K full-wave quads (i, i+stride, ...) together,
+//          pushes all 4K keys, drains Q1 down below 64 and only then loads
+//          again, so no drain's gather queues behind a stream load (vector
+//          loads retire in issue order, and pfq4's prefetched pair sits ahead
+//          of every gather of its iteration). Measured, that is worth what
+//          pfq4's prefetch is worth and no more, K = 2, 4, 8 alike; the gain
+//          over pfq4 comes from FA = 19.
+// Fills. Q1CAP >= 320: a wave-uniform guard before each quad drains full
+// batches while n1 + 256 > Q1CAP (then n1 > Q1CAP-256 >= 64, so a full batch
+// is there), leaving n1 <= Q1CAP-256; the quad's four pushes add <= 256, so
+// Q1 <= Q1CAP. Q1CAP == 128 cannot take a whole quad and keeps pfq4's drain
+// after each key's push instead (Q1 <= 127). Either way every drain1 is
+// followed at once by the tail's own threshold drains, so Q2 <= 127, Q3 <= 127
+// and Q2 + Q3 <= 190 = QS as proved above pfq4. LDS: 2^FA/8 + 32 KB folds +
+// 3,584 B groups + 128*Q1CAP B Q1 + 18,240 B Q2/Q3, static, 1 block/CU.
+// Every fill comes from a ballot: all loop conditions are wave-uniform, and
+// the kernel is blockDim-agnostic (64..1024). Row ids are 32-bit.
+// ---------------------------------------------------------------------------
+template <int FA, int Q1CAP, int K>
+__global__ __launch_bounds__(BLOCK_Q21) void
+k_q21_star_agg_pfq5(const int32_t* __restrict__ pk, const int32_t* __restrict__ sk,
+                    const int32_t* __restrict__ od, const int32_t* __restrict__ rv,
+                    uint64_t n, const uint32_t* __restrict__ folda,
+                    const uint32_t* __restrict__ foldb, int64_t psmin, uint64_t psint,
+                    const uint16_t* __restrict__ pfirstc,
+                    const uint16_t* __restrict__ pay_vals, uint32_t n_pay,
+                    const uint32_t* __restrict__ sbits, int64_t ssmin, uint64_t ssint,
+                    const uint16_t* __restrict__ dfirst, int64_t dmin,
+                    unsigned long long* __restrict__ group_sums) {
+    static_assert(FA == 18 || FA == 19, "fold A is one of the table's two masked folds");
+    static_assert(Q1CAP == 128 || Q1CAP >= 320, "see the fill bounds above");
+    static_assert(K >= 1 && (K == 1 || Q1CAP >= 320), "a burst needs the per-quad guard");
+    constexpr bool PERKEY = Q1CAP == 128;
+    constexpr int QS = 126 + 64;
+    constexpr uint32_t WA = 1u << (FA - 5);
+    __shared__ uint32_t pfa[WA];
+    __shared__ uint32_t pfb[1 << 13];
+    __shared__ unsigned long long g[7 * NBC];
+    __shared__ int2 q1[BLOCK_Q21 / WAVE][Q1CAP];    // {pk, row32}
+    __shared__ uint32_t qrow[BLOCK_Q21 / WAVE][QS]; // Q2 up from 0, Q3 down from QS-1
+    __shared__ uint16_t qbr[BLOCK_Q21 / WAVE][QS];
+    for (uint32_t w = threadIdx.x; w < WA; w += blockDim.x) pfa[w] = folda[w];
+    for (uint32_t w = threadIdx.x; w < (1u << 13); w += blockDim.x) pfb[w] = foldb[w];
+    for (uint32_t j = threadIdx.x; j < 7 * NBC; j += blockDim.x) g[j] = 0;
+    __syncthreads();
+    const int wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t n1 = 0, n2 = 0, n3 = 0; // wave-uniform fills (ballot counts)
+    const uint64_t n4 = n / 4;
+    const int4* __restrict__ pk4 = (const int4*)pk;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    // the three drains are pfq4's at B = 1, over ranks and the compact g;
+    // cnt = 64 for a full batch, the fill at the final flush
+    auto drain3 = [&](uint32_t cnt) {
+        bool act = lane < cnt;
+        uint32_t slot = QS - 1 - (n3 - cnt + lane);
+        uint32_t r = act ? qrow[wid][slot] : 0u;
+        uint32_t b = act ? qbr[wid][slot] : 0u;
+        n3 -= cnt;
+        if (act) {
+            int32_t o = od[r];
+            int32_t v = rv[r];
+            uint32_t y = dfirst[o - dmin];
+            atomicAdd(&g[(y - 1) * NBC + (b - 1)], (unsigned long long)(int64_t)v);
+        }
+    };
+    auto drain2 = [&](uint32_t cnt) {
+        bool act = lane < cnt;
+        uint32_t r = act ? qrow[wid][n2 - cnt + lane] : 0u;
+        uint32_t b = act ? qbr[wid][n2 - cnt + lane] : 0u;
+        n2 -= cnt;
+        bool pass = false;
+        if (act) {
+            uint32_t sidx = (uint32_t)(sk[r] - ssmin);
+            pass = sidx < ssint && ((sbits[sidx >> 5] >> (sidx & 31)) & 1u);
+        }
+        uint64_t m = __ballot(pass);
+        if (m) {
+            if (pass) {
+                uint32_t slot = QS - 1 - (n3 + __popcll(m & below));
+                qrow[wid][slot] = r;
+                qbr[wid][slot] = (uint16_t)b;
+            }
+            n3 += __popcll(m);
+            if (n3 >= 64) drain3(64);
+        }
+    };
+    auto drain1 = [&](uint32_t cnt) {
+        bool act = lane < cnt;
+        int2 e = act ? q1[wid][n1 - cnt + lane] : make_int2(1, 0);
+        n1 -= cnt;
+        uint32_t rank1 = act ? pfirstc[e.x - 1] : 0u; // exact category filter (0 = fail)
+        uint64_t m = __ballot(rank1 != 0);
+        if (m) {
+            if (rank1) {
+                uint32_t slot = n2 + __popcll(m & below);
+                qrow[wid][slot] = (uint32_t)e.y;
+                qbr[wid][slot] = (uint16_t)rank1;
+            }
+            n2 += __popcll(m);
+            if (n2 >= 64) drain2(64);
+        }
+    };
+    auto push = [&](int32_t key, uint32_t row, bool inb) {
+        uint32_t idx = (uint32_t)(key - psmin);
+        bool in = inb & (idx < psint);
+        uint32_t ia = (in ? idx : 0u) & ((1u << FA) - 1);
+        uint32_t ib = ((in ? idx : 0u) * 2654435761u) >> 14;
+        bool maybe = in & (pfa[ia >> 5] >> (ia & 31)) & (pfb[ib >> 5] >> (ib & 31)) & 1u;
+        uint64_t m = __ballot(maybe);
+        if (m) {
+            if (maybe) q1[wid][n1 + __popcll(m & below)] = make_int2(key, (int32_t)row);
+            n1 += __popcll(m);
+            if constexpr (PERKEY)
+                if (n1 >= 64) drain1(64);
+        }
+    };
+    auto quad = [&](int4 p, uint64_t qi, bool inb) {
+        if constexpr (!PERKEY)
+            while (n1 + 256 > Q1CAP) drain1(64); // overflow guard, once per quad
+        #pragma unroll
+        for (int j = 0; j < 4; j++) push((&p.x)[j], (uint32_t)(qi * 4 + j), inb);
+    };
+    auto ld4nt = [&](const int4* p, uint64_t i) {
+        const uint64_t* q = (const uint64_t*)(p + i);
+        uint64_t lo = __builtin_nontemporal_load(q);
+        uint64_t hi = __builtin_nontemporal_load(q + 1);
+        int4 v;
+        v.x = (int32_t)lo; v.y = (int32_t)(lo >> 32);
+        v.z = (int32_t)hi; v.w = (int32_t)(hi >> 32);
+        return v;
+    };
+    uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (uint64_t)wid * WAVE;
+    uint64_t i = base + lane;
+    // bursts of K quads, all of them full-wave
+    for (; base + (K - 1) * stride + WAVE <= n4; base += K * stride, i += K * stride) {
+        int4 p[K];
+        #pragma unroll
+        for (int k = 0; k < K; k++) p[k] = ld4nt(pk4, i + k * stride);
+        #pragma unroll
+        for (int k = 0; k < K; k++) quad(p[k], i + k * stride, true);
+        while (n1 >= 64) drain1(64);
+    }
+    for (; base < n4; base += stride, i += stride) {
+        bool inb = i < n4;
+        int4 p4 = inb ? pk4[i] : make_int4(0, 0, 0, 0);
+        quad(p4, i, inb);
+        while (n1 >= 64) drain1(64);
+    }
+    // final flush, in stage order: each partial drain leaves the next stage
+    // below its threshold again before that stage's own partial drain
+    if (n1 > 0) drain1(n1);
+    if (n2 > 0) drain2(n2);
+    if (n3 > 0) drain3(n3);
+    // scalar row tail (n % 4): exact path
+    uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t r = n4 * 4 + tid; r < n; r += stride) {
+        uint32_t idx = (uint32_t)(pk[r] - psmin);
+        if (idx >= psint) continue;
+        uint32_t rank1 = pfirstc[pk[r] - 1];
+        if (!rank1) continue;
+        uint32_t sidx = (uint32_t)(sk[r] - ssmin);
+        if (sidx >= ssint || !((sbits[sidx >> 5] >> (sidx & 31)) & 1u)) continue;
+        uint32_t year1 = dfirst[od[r] - dmin];
+        atomicAdd(&g[(year1 - 1) * NBC + (rank1 - 1)], (unsigned long long)(int64_t)rv[r]);
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < 7 * n_pay; j += blockDim.x) {
+        uint32_t y = j / n_pay, r = j - y * n_pay;
+        unsigned long long v = g[y * NBC + r];
+        if (v != 0) atomicAdd(&group_sums[y * 1000 + pay_vals[r] - 1], v);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Two-stream pipelined q21 (GPUE_Q21_PIPE=1): the fused kernel's streaming
 // leg (1.57 ms) and its part-probe gather leg (2.32 ms) measured fully
 // ADDITIVE (profiles/q21_decomp.log) — so split them into an operator pair
@@ -5525,6 +5794,12 @@ static bool q21_pf() {
     return v == 1;
 }
 
+// The GPUE_Q21_PF9_VAR that runs when GPUE_Q21_PF is unset and the part table
+// qualifies for mode 9 (0 would leave mode 8 var 11 the default everywhere).
+// Var 4's slowest run was faster than the parent default's fastest in two
+// sessions of 5 interleaved runs (profiles/r04_q21_compact_ab.log)
+static constexpr int Q21_PF9_DEFAULT_VAR = 4;
+
 extern "C" int gpue_q21_star_agg_async(gpue_session* s, gpue_join_table* parts,
                                        gpue_join_table* supps, gpue_join_table* dates,
                                        gpue_dbuf* pk, gpue_dbuf* sk, gpue_dbuf* od,
@@ -5539,7 +5814,13 @@ int gpue_q21_star_agg_async(gpue_session* s, gpue_join_table* parts, gpue_join_t
     HIP_CHECK(hipMemsetAsync(group_sums->ptr, 0, NG_Q21 * sizeof(int64_t), s->stream));
     if (q21_pf() && parts->prefilter) {
         const char* e = getenv("GPUE_Q21_PF");
-        int mode = e ? atoi(e) : 8; // staged cascade + prefetched pk stream
+        // mode 9 (compact groups, k_q21_star_agg_pfq5) needs the part table's
+        // dense payload rank and the 1000-brand output layout; it is the
+        // default where it can run, mode 8 var 11 stays the default elsewhere
+        const bool compact_ok = parts->first16c && parts->prefilter2 && parts->prefilter2w &&
+                                parts->pay_max <= 1000 && n <= UINT32_MAX;
+        int mode = e ? atoi(e) : (compact_ok && Q21_PF9_DEFAULT_VAR > 0) ? 9 : 8;
+                                    // 8 = staged cascade + prefetched pk stream
                                     // over mode 7's deferred loads: 1.015-
                                     // 1.040 (median 1.027) vs mode 7's 1.105-
                                     // 1.132 (median 1.109) ms/step, 5 runs
@@ -5574,7 +5855,37 @@ int gpue_q21_star_agg_async(gpue_session* s, gpue_join_table* parts, gpue_join_t
         };
         // modes 7 and 8 queue row ids as 32 bits
         ARG_CHECK((mode != 7 && mode != 8) || n <= UINT32_MAX);
-        if (mode == 8) { // staged cascade + prefetched pk stream
+        if (mode == 9) { // compact groups + wider fold / burst-drained pk stream
+            ARG_CHECK(compact_ok);
+            // GPUE_Q21_PF9_VAR, read per call: the (FA, Q1CAP, K) of
+            // k_q21_star_agg_pfq5. 1 = (18, 128, 1) the control: compact
+            // groups only; 2 = (19, 128, 1) the wider fold A; 3 = (18, 384, 4)
+            // the burst; 4 = (19, 320, 4) both. Medians of 5 interleaved
+            // runs, ms/step, against mode 8 var 11's 1.0241 and the parent
+            // commit's binary's 1.0163: 1 = 1.0898, 2 = 1.0437, 3 = 1.0324,
+            // 4 = 0.9999 (0.9913-1.0004, below the parent's fastest 1.0140)
+            int var = (int)env_cap("GPUE_Q21_PF9_VAR",
+                                   Q21_PF9_DEFAULT_VAR > 0 ? Q21_PF9_DEFAULT_VAR : 1);
+            ARG_CHECK(var >= 1 && var <= 4);
+            auto launch9 = [&](auto kern, const uint32_t* folda) {
+                hipLaunchKernelGGL(kern, dim3(env_cap("GPUE_GRID_PF", def_grid)),
+                                   dim3(tpb), 0, s->stream, (const int32_t*)pk->ptr,
+                                   (const int32_t*)sk->ptr, (const int32_t*)od->ptr,
+                                   (const int32_t*)rv->ptr, n, folda,
+                                   parts->prefilter2 + (1u << 13), parts->set_min,
+                                   (uint64_t)(parts->set_max - parts->set_min + 1),
+                                   parts->first16c, parts->pay_vals, parts->n_pay,
+                                   supps->bitset, supps->set_min,
+                                   (uint64_t)(supps->set_max - supps->set_min + 1),
+                                   dates->first16, dates->min_key,
+                                   (unsigned long long*)group_sums->ptr);
+            };
+            if (var == 1) launch9(k_q21_star_agg_pfq5<18, 128, 1>, parts->prefilter2);
+            else if (var == 2) launch9(k_q21_star_agg_pfq5<19, 128, 1>, parts->prefilter2w);
+            else if (var == 3) launch9(k_q21_star_agg_pfq5<18, 384, 4>, parts->prefilter2);
+            else launch9(k_q21_star_agg_pfq5<19, 320, 4>, parts->prefilter2w);
+        }
+        else if (mode == 8) { // staged cascade + prefetched pk stream
             // GPUE_Q21_PF8_VAR, read per call: tens digit = PREFETCH, ones
             // digit = B of k_q21_star_agg_pfq4 (10 = prefetch only, 1 =
             // cascade only, 11 / 12 = both at B = 1 / 2). Medians of 5
