@@ -838,6 +838,83 @@ int gpue_q3_probe_accum(gpue_session* s, gpue_dbuf* lk, gpue_dbuf* ext, gpue_dbu
 int gpue_agg_table_size(gpue_session* s, gpue_agg_table* t, uint64_t* n_groups);
 int gpue_agg_table_ensure(gpue_session* s, gpue_agg_table* t, uint64_t additional_rows);
 
+/* ---- general GROUP BY: multi-key, multi-aggregate, NULL-aware -----------
+ * The whole AggHashMapWithKey::compute_agg_states + update_batch /
+ * merge_batch + convert_hash_map_to_chunk chain (reference agg_hash_map.h,
+ * aggregator.cpp, exprs/agg/aggregate.h) behind one persistent, growable
+ * table whose key / aggregate layout is fixed at creation. It takes the
+ * nullable column format gpue_pred_eval_mask and gpue_expr_project produce:
+ * a value column plus a u8 null column.
+ *
+ * Keys: 1..GPUE_GA_MAX_KEYS columns, GPUE_PT_I32 (sign-extended) or
+ * GPUE_PT_I64. Every 64-bit pattern is a legal key value, ~0 included (the
+ * table has no key sentinel). A row is NULL on key i iff key_nulls[i][row]
+ * is nonzero. NULL equals NULL for grouping, and the value stored under a
+ * NULL key is never read: rows that are NULL on key i and equal elsewhere
+ * are one group whatever sits in their value cells. key_nulls (or an entry)
+ * may be NULL for a key declared nullable — no NULLs in this chunk; a
+ * non-NULL null buffer for a key declared non-nullable is GPUE_ERR_ARG.
+ *
+ * Aggregates: 0..GPUE_GA_MAX_AGGS (0 = DISTINCT). COUNT_STAR counts rows and
+ * takes no input column; COUNT counts non-NULL inputs; SUM (wrapping mod
+ * 2^64, as gpue_hash_agg_sum_u64), MIN and MAX ignore NULL inputs. The same
+ * rule as for keys holds for agg_nulls. Output nullability is static:
+ * COUNT_STAR and COUNT never; SUM / MIN / MAX iff their input was declared
+ * nullable, and a group that saw no non-NULL input emits NULL (value 0, null
+ * byte 1). All aggregate outputs are int64.
+ *
+ * GPUE_GA_MERGE (push flag): the inputs are partial states as emit produces
+ * them — every aggregate input is an int64 column, COUNT_STAR has one too,
+ * COUNT / COUNT_STAR add their input, SUM / MIN / MAX combine as usual, a
+ * NULL partial is skipped (merge_batch; what the cnts argument of
+ * gpue_hash_agg_push_u64 covers for one column).
+ *
+ * emit: keys in their own types (0 under NULL) with u8 1/0 null columns for
+ * nullable keys (out_key_nulls entries of non-nullable keys are ignored),
+ * then the aggregates with null columns for nullable outputs. Order is table
+ * order; results are a set, compare key-sorted. The table stays intact: push
+ * -> emit -> push -> emit is legal. More groups than max_out: GPUE_ERR_ARG
+ * with *n_groups set to the true count, nothing written.
+ *
+ * Never full: push works in sub-batches of at most 2^20 rows and, before
+ * each, doubles + rehashes on device until load <= 5/8 even if every row of
+ * the sub-batch were a new group (the gpue_agg_table_ensure rule);
+ * capacity_hint is only a starting size. No lane ever waits on another
+ * lane's store: every loop is a probe walk bounded by the capacity
+ * (DESIGN.md §4g).
+ *
+ * GPUE_ERR_ARG, before any launch or allocation, for: n_keys outside
+ * 1..GPUE_GA_MAX_KEYS, n_aggs outside 0..GPUE_GA_MAX_AGGS, an unknown type,
+ * function or flag, n_rows >= 2^32, any buffer shorter than n_rows (or
+ * max_out) elements, a missing input or output column (a nullable output
+ * needs its null column), an output that overlaps another output.
+ * n_rows == 0 returns GPUE_OK. No GROUP BY at all (n_keys == 0) and int128
+ * sums are not covered: gpue_hash_agg_sum128_u64 stays the int128 entry. */
+typedef struct gpue_group_agg gpue_group_agg;
+#define GPUE_GA_MAX_KEYS 4
+#define GPUE_GA_MAX_AGGS 8
+#define GPUE_GA_COUNT_STAR 0   /* no input column in normal mode */
+#define GPUE_GA_COUNT 1        /* COUNT(col): non-NULL rows */
+#define GPUE_GA_SUM 2          /* int64, wrapping mod 2^64 like the existing SUM */
+#define GPUE_GA_MIN 3
+#define GPUE_GA_MAX 4
+#define GPUE_GA_MERGE 1        /* push flag: inputs are partial states */
+int gpue_group_agg_create(gpue_session* s, const int32_t* key_type /* GPUE_PT_I32 / _I64 */,
+                          const int32_t* key_nullable, int n_keys,
+                          const int32_t* agg_fn,
+                          const int32_t* agg_type /* GPUE_PT_*; ignored for COUNT_STAR */,
+                          const int32_t* agg_nullable, int n_aggs /* 0..8; 0 = DISTINCT */,
+                          uint64_t capacity_hint, gpue_group_agg** out);
+int gpue_group_agg_push(gpue_session* s, gpue_group_agg* t, gpue_dbuf** key_cols,
+                        gpue_dbuf** key_nulls, gpue_dbuf** agg_cols, gpue_dbuf** agg_nulls,
+                        uint64_t n_rows, int flags);
+int gpue_group_agg_size(gpue_session* s, gpue_group_agg* t, uint64_t* n_groups);
+int gpue_group_agg_emit(gpue_session* s, gpue_group_agg* t, gpue_dbuf** out_keys,
+                        gpue_dbuf** out_key_nulls, gpue_dbuf** out_aggs,
+                        gpue_dbuf** out_agg_nulls, uint64_t max_out, uint64_t* n_groups);
+int gpue_group_agg_reset(gpue_group_agg* t);
+void gpue_group_agg_destroy(gpue_group_agg* t);
+
 /* ---- pinned double-buffered H2D ingest ----
  * north_star's "columnar batches pinned and streamed to HBM": two
  * hipHostMalloc staging buffers on the session's second stream; while chunk

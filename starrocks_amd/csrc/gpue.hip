@@ -7686,6 +7686,704 @@ int gpue_hash_agg_emit_u64(gpue_session* s, gpue_agg_table* at, gpue_dbuf* out_k
 }
 
 // ---------------------------------------------------------------------------
+// General GROUP BY (gpue_group_agg_*, gpue.h "general GROUP BY"; DESIGN.md
+// §4g): 1..4 int32/int64 key columns with NULLs, 0..8 aggregates with NULL
+// inputs, merge mode, a table that grows. The kernels above claim a slot by
+// CAS-ing the 8-byte key itself into it; a key tuple with null flags does
+// not fit one CAS, and "lock, write the key, publish" would make lanes wait
+// on a store from a lane that may sit in their own wave. This protocol has
+// no such wait — every key comparison reads memory that no lane writes
+// during the kernel:
+//   slot word (64 bit): 0 = EMPTY, else bit 63 set | bit 62 FRESH | 4 key
+//   null flags | 26-bit hash fingerprint | 32-bit index. Flags and
+//   fingerprint are compared as one 30-bit tag, so a settled slot's null
+//   flags live in its word and cost no load of their own.
+//   SETTLED slot: its key tuple sits in the table's per-slot key store,
+//     written by an earlier kernel.
+//   FRESH slot: claimed in this push kernel; the index is the claimant's row
+//     in the current sub-batch, and the key tuple is read from the INPUT
+//     key columns at that row.
+// A slot word changes at most once per push kernel (EMPTY -> FRESH, by
+// CAS), so a plain load can only be stale as EMPTY, and the CAS that follows
+// returns the true word. k_ga_settle then copies the keys of the claimed
+// slots (from a claim list: O(new groups), not O(capacity)) into the key
+// store and clears FRESH. Every loop is a probe walk bounded by the capacity.
+// ---------------------------------------------------------------------------
+static constexpr unsigned long long GA_OCC = 1ull << 63;
+static constexpr unsigned long long GA_FRESH = 1ull << 62;
+static constexpr unsigned long long GA_FP_MASK = 0x3FFFFFFF00000000ull; // the 30-bit tag
+static constexpr unsigned long long GA_HASH_BITS = 0x03FFFFFF00000000ull;
+static constexpr int GA_NB_SHIFT = 58;
+static constexpr uint64_t GA_SUB_BATCH = 1ull << 20;
+static constexpr uint64_t GA_MAX_CAP = 1ull << 31; // slot indexes fit the claim list's u32
+// wave-level pre-combine is on while the table holds 1..32 groups: measured
+// 1.35-6.8x faster at 16-32 groups, mixed at 64, 1.8-3.3x slower at 1000
+// 
+static constexpr uint64_t GA_COMBINE_MAX_GROUPS = 32;
+enum { GA_OP_ADD1 = 0, GA_OP_ADD1_NN = 1, GA_OP_ADDV = 2, GA_OP_MIN = 3, GA_OP_MAX = 4 };
+
+// device view of the table: per-slot word, key store and state words. State
+// word w of slot s sits at st[s * slot_stride + w * word_stride] — (n_words,
+// 1) is the AoS layout, (1, cap) the SoA one. Words 0..n_aggs-1 are the
+// aggregate states; word n_aggs (present iff seen_mask != 0) holds one "saw
+// a non-NULL input" bit per nullable SUM / MIN / MAX.
+struct GaTable {
+    unsigned long long* slots;
+    long long* kstore; // [key * cap + slot], 0 under NULL
+    unsigned long long* st;
+    uint64_t cap; // power of two
+    uint64_t slot_stride, word_stride;
+    uint32_t n_keys, n_aggs, n_words, seen_mask;
+    uint8_t aop[GPUE_GA_MAX_AGGS]; // GA_OP_* of each state (its identity at init)
+};
+
+// one sub-batch of input columns, already offset to its first row
+struct GaInput {
+    const void* kcol[GPUE_GA_MAX_KEYS];
+    const uint8_t* knul[GPUE_GA_MAX_KEYS];
+    const void* acol[GPUE_GA_MAX_AGGS];
+    const uint8_t* anul[GPUE_GA_MAX_AGGS];
+    uint8_t k64[GPUE_GA_MAX_KEYS];
+    uint8_t a64[GPUE_GA_MAX_AGGS];
+    uint8_t aop[GPUE_GA_MAX_AGGS]; // per push: merge mode turns the counts into ADDV
+};
+
+struct GaEmit {
+    void* okey[GPUE_GA_MAX_KEYS];
+    uint8_t* oknul[GPUE_GA_MAX_KEYS];
+    long long* oagg[GPUE_GA_MAX_AGGS];
+    uint8_t* oanul[GPUE_GA_MAX_AGGS];
+    uint8_t k64[GPUE_GA_MAX_KEYS];
+};
+
+struct GaKey {
+    long long v[GPUE_GA_MAX_KEYS]; // 0 under NULL and past n_keys
+    uint32_t nb;                   // bit k = NULL on key k
+};
+
+__device__ static inline GaKey ga_load_key(const GaInput& in, uint32_t n_keys, uint64_t row) {
+    GaKey k;
+    k.nb = 0;
+#pragma unroll
+    for (int c = 0; c < GPUE_GA_MAX_KEYS; c++) {
+        long long v = 0;
+        if (c < (int)n_keys) {
+            if (in.knul[c] && in.knul[c][row]) k.nb |= 1u << c;
+            else v = in.k64[c] ? ((const long long*)in.kcol[c])[row]
+                               : (long long)((const int*)in.kcol[c])[row];
+        }
+        k.v[c] = v;
+    }
+    return k;
+}
+
+__device__ static inline unsigned long long ga_tag(uint64_t h, uint32_t nb) {
+    return (h & GA_HASH_BITS) | ((unsigned long long)nb << GA_NB_SHIFT);
+}
+
+// the key tuple of settled slot s, whose word is `word`
+__device__ static inline GaKey ga_store_key(const GaTable& t, uint64_t s,
+                                            unsigned long long word) {
+    GaKey k;
+    k.nb = (uint32_t)(word >> GA_NB_SHIFT) & 0xFu;
+#pragma unroll
+    for (int c = 0; c < GPUE_GA_MAX_KEYS; c++)
+        k.v[c] = c < (int)t.n_keys ? t.kstore[(uint64_t)c * t.cap + s] : 0;
+    return k;
+}
+
+__device__ static inline bool ga_key_eq(const GaKey& a, const GaKey& b) {
+    bool eq = a.nb == b.nb;
+#pragma unroll
+    for (int c = 0; c < GPUE_GA_MAX_KEYS; c++) eq = eq && a.v[c] == b.v[c];
+    return eq;
+}
+
+// NULL cells hash as the constant 0 they are canonicalised to; the null
+// flags are mixed in, so (NULL) and (0) start their walks apart
+__device__ static inline uint64_t ga_hash(const GaKey& k, uint32_t n_keys) {
+    uint64_t h = 0x9E3779B97F4A7C15ull * (uint64_t)(k.nb + 1);
+#pragma unroll
+    for (int c = 0; c < GPUE_GA_MAX_KEYS; c++) {
+        if (c < (int)n_keys) {
+            h = (h ^ (uint64_t)k.v[c]) * 0xBF58476D1CE4E5B9ull;
+            h ^= h >> 31;
+        }
+    }
+    h *= 0x94D049BB133111EBull;
+    return h ^ (h >> 29);
+}
+
+__device__ static inline long long ga_identity(uint32_t op) {
+    return op == GA_OP_MIN ? 0x7FFFFFFFFFFFFFFFll
+                           : op == GA_OP_MAX ? (long long)0x8000000000000000ull : 0ll;
+}
+
+__device__ static inline void ga_apply(unsigned long long* w, uint32_t op, long long v) {
+    if (op == GA_OP_MIN) atomicMin((long long*)w, v);
+    else if (op == GA_OP_MAX) atomicMax((long long*)w, v);
+    else atomicAdd(w, (unsigned long long)v);
+}
+
+// bits only ever get set, so a stale plain load costs one spare atomic at most
+__device__ static inline void ga_mark_seen(unsigned long long* w, unsigned long long bits) {
+    if ((*(volatile unsigned long long*)w & bits) != bits) atomicOr(w, bits);
+}
+
+__device__ static inline long long ga_wave_reduce(long long v, uint32_t op) {
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        long long o = __shfl_xor(v, off, WAVE);
+        v = op == GA_OP_MIN ? (o < v ? o : v) : op == GA_OP_MAX ? (o > v ? o : v) : v + o;
+    }
+    return v;
+}
+
+__global__ void k_ga_init(const GaTable t) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    uint64_t total = t.cap * t.n_words;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        uint64_t s = i / t.n_words;
+        uint32_t w = (uint32_t)(i % t.n_words);
+        t.st[s * t.slot_stride + w * t.word_stride] =
+            w < t.n_aggs ? (unsigned long long)ga_identity(t.aop[w]) : 0ull;
+    }
+}
+
+// ctl[0] = slots claimed since the table was created or reset (claim_base of
+// them before this launch, so nothing is cleared between launches), ctl[1] =
+// error latch (AGG_ERR_FULL).
+// combine: false, one atomic per row and state; true, the lanes of a wave that
+// resolved to one slot reduce in-wave first and their first lane issues one
+// atomic per state — the host turns it on for tables of a handful of groups,
+// where all 64 lanes hit the same few addresses.
+__global__ __launch_bounds__(BLOCK) void
+k_ga_push(const GaTable t, const GaInput in, uint64_t n, uint32_t* __restrict__ claims,
+          unsigned long long* __restrict__ ctl, uint64_t claim_base, bool combine) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t mask = t.cap - 1;
+    const int lane = threadIdx.x & (WAVE - 1);
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += stride) {
+        const uint64_t i = base + threadIdx.x;
+        bool ok = i < n, claimed = false;
+        uint64_t s = 0;
+        if (ok) {
+            const GaKey k = ga_load_key(in, t.n_keys, i);
+            const uint64_t h = ga_hash(k, t.n_keys);
+            const unsigned long long fp = ga_tag(h, k.nb);
+            const unsigned long long fresh = GA_OCC | GA_FRESH | fp | (uint32_t)i;
+            s = h & mask;
+            uint64_t left = t.cap;
+            for (;;) {
+                unsigned long long cur = t.slots[s];
+                if (cur == 0) {
+                    cur = atomicCAS(&t.slots[s], 0ull, fresh);
+                    if (cur == 0) { claimed = true; break; }
+                }
+                if ((cur & GA_FP_MASK) == fp) {
+                    const GaKey o = (cur & GA_FRESH) ? ga_load_key(in, t.n_keys, (uint32_t)cur)
+                                                     : ga_store_key(t, s, cur);
+                    if (ga_key_eq(k, o)) break;
+                }
+                s = (s + 1) & mask;
+                if (--left == 0) { atomicOr(&ctl[1], (unsigned long long)AGG_ERR_FULL); ok = false; break; }
+            }
+        }
+        // claim list: one counter add per wave
+        const uint64_t cm = __ballot(claimed);
+        if (cm) {
+            const int leader = __ffsll((unsigned long long)cm) - 1;
+            unsigned long long cbase = 0;
+            if (lane == leader)
+                cbase = atomicAdd(&ctl[0], (unsigned long long)__popcll(cm)) - claim_base;
+            cbase = __shfl(cbase, leader, WAVE);
+            const unsigned long long ci = cbase + __popcll(cm & ((1ull << lane) - 1));
+            if (claimed) {
+                if (ci < n) claims[ci] = (uint32_t)s; // at most one claim per row
+                else atomicOr(&ctl[1], (unsigned long long)AGG_ERR_FULL);
+            }
+        }
+        if (t.n_aggs == 0) continue;
+        // this row's contribution to every state
+        long long av[GPUE_GA_MAX_AGGS];
+        uint32_t valid = 0;
+#pragma unroll
+        for (int a = 0; a < GPUE_GA_MAX_AGGS; a++) {
+            av[a] = 1;
+            if (ok && a < (int)t.n_aggs) {
+                const uint32_t op = in.aop[a];
+                if (op == GA_OP_ADD1 || !(in.anul[a] && in.anul[a][i])) {
+                    valid |= 1u << a;
+                    if (op >= GA_OP_ADDV)
+                        av[a] = in.a64[a] ? ((const long long*)in.acol[a])[i]
+                                          : (long long)((const int*)in.acol[a])[i];
+                }
+            }
+        }
+        unsigned long long* const st = t.st + s * t.slot_stride;
+        if (!combine) {
+#pragma unroll
+            for (int a = 0; a < GPUE_GA_MAX_AGGS; a++)
+                if (valid >> a & 1) ga_apply(st + a * t.word_stride, in.aop[a], av[a]);
+            const unsigned long long sb = valid & t.seen_mask;
+            if (sb) ga_mark_seen(st + t.n_aggs * t.word_stride, sb);
+            continue;
+        }
+        // one atomic per distinct slot of the wave; at most 64 rounds, each
+        // retires the lanes of one slot
+        uint64_t todo = __ballot(ok);
+        while (todo) {
+            const int leader = __ffsll((unsigned long long)todo) - 1;
+            const uint64_t s0 = __shfl((unsigned long long)s, leader, WAVE);
+            const bool mine = ok && s == s0;
+            todo &= ~__ballot(mine);
+            unsigned long long sb = 0;
+#pragma unroll
+            for (int a = 0; a < GPUE_GA_MAX_AGGS; a++) {
+                if (a >= (int)t.n_aggs) break;
+                const bool c = mine && (valid >> a & 1);
+                const uint64_t cb = __ballot(c);
+                if (cb == 0) continue; // wave-uniform
+                const uint32_t op = in.aop[a];
+                long long r;
+                if (op <= GA_OP_ADD1_NN) r = __popcll(cb);
+                else r = ga_wave_reduce(c ? av[a] : ga_identity(op), op);
+                if (lane == leader) ga_apply(st + a * t.word_stride, op, r);
+                sb |= 1ull << a;
+            }
+            sb &= t.seen_mask;
+            if (sb && lane == leader) ga_mark_seen(st + t.n_aggs * t.word_stride, sb);
+        }
+    }
+}
+
+__global__ void k_ga_settle(const GaTable t, const GaInput in,
+                            const uint32_t* __restrict__ claims, uint64_t n_claims) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_claims;
+         i += stride) {
+        const uint64_t s = claims[i];
+        const unsigned long long w = t.slots[s];
+        const GaKey k = ga_load_key(in, t.n_keys, (uint32_t)w);
+#pragma unroll
+        for (int c = 0; c < GPUE_GA_MAX_KEYS; c++)
+            if (c < (int)t.n_keys) t.kstore[(uint64_t)c * t.cap + s] = k.v[c];
+        t.slots[s] = w & (GA_OCC | GA_FP_MASK);
+    }
+}
+
+// growth: hashes re-derived from the key store; old keys are unique, so the
+// claim needs no key compare and the payload stores no atomics (k_agg_rehash)
+__global__ void k_ga_rehash(const GaTable o, const GaTable nt,
+                            unsigned long long* __restrict__ ctl) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t mask = nt.cap - 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < o.cap;
+         i += stride) {
+        const unsigned long long ow = o.slots[i];
+        if (ow == 0) continue;
+        const GaKey k = ga_store_key(o, i, ow);
+        const uint64_t h = ga_hash(k, o.n_keys);
+        const unsigned long long word = GA_OCC | ga_tag(h, k.nb);
+        uint64_t s = h & mask, left = nt.cap;
+        while (atomicCAS(&nt.slots[s], 0ull, word) != 0) {
+            s = (s + 1) & mask;
+            if (--left == 0) break;
+        }
+        if (left == 0) { atomicOr(&ctl[1], (unsigned long long)AGG_ERR_FULL); continue; }
+#pragma unroll
+        for (int c = 0; c < GPUE_GA_MAX_KEYS; c++)
+            if (c < (int)o.n_keys) nt.kstore[(uint64_t)c * nt.cap + s] = k.v[c];
+        for (uint32_t w = 0; w < o.n_words; w++)
+            nt.st[s * nt.slot_stride + w * nt.word_stride] =
+                o.st[i * o.slot_stride + w * o.word_stride];
+    }
+}
+
+// convert_hash_map_to_chunk: the tiled two-phase count / scan / write shape
+// of k_hash_agg_emit_wide over the occupied slots
+__global__ void k_ga_emit(const GaTable t, const GaEmit e, uint64_t max_out,
+                          unsigned long long* __restrict__ cursor) {
+    const uint64_t nb = gridDim.x, cap = t.cap;
+    const uint64_t tile = (cap + nb - 1) / nb;
+    const uint64_t lo_ = (uint64_t)blockIdx.x * tile;
+    const uint64_t hi_ = min(lo_ + tile, cap);
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    __shared__ uint64_t wsum[BLOCK / WAVE + 1];
+    uint64_t cnum = 0;
+    for (uint64_t s = lo_ + threadIdx.x; s < hi_; s += blockDim.x) cnum += (t.slots[s] != 0);
+    for (int off = WAVE / 2; off > 0; off >>= 1)
+        cnum += __shfl_down((unsigned long long)cnum, off, WAVE);
+    if (lane == 0) wsum[wid] = cnum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t tot = 0;
+        for (int w = 0; w < BLOCK / WAVE; w++) tot += wsum[w];
+        wsum[BLOCK / WAVE] = atomicAdd(cursor, (unsigned long long)tot);
+    }
+    __syncthreads();
+    uint64_t offset = wsum[BLOCK / WAVE];
+    __shared__ uint64_t wbase[BLOCK / WAVE + 1];
+    for (uint64_t base = lo_; base < hi_; base += blockDim.x) {
+        const uint64_t s = base + threadIdx.x;
+        const bool has = (s < hi_) && (t.slots[s] != 0);
+        const uint64_t m = __ballot(has);
+        if (lane == 0) wbase[wid] = __popcll(m);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint64_t acc = offset;
+            for (int w = 0; w < BLOCK / WAVE; w++) {
+                uint64_t v = wbase[w];
+                wbase[w] = acc;
+                acc += v;
+            }
+            wbase[BLOCK / WAVE] = acc;
+        }
+        __syncthreads();
+        if (has) {
+            const uint64_t pos = wbase[wid] + __popcll(m & ((1ull << lane) - 1));
+            if (pos < max_out) {
+                const GaKey k = ga_store_key(t, s, t.slots[s]);
+#pragma unroll
+                for (int c = 0; c < GPUE_GA_MAX_KEYS; c++) {
+                    if (c >= (int)t.n_keys) break;
+                    if (e.k64[c]) ((long long*)e.okey[c])[pos] = k.v[c];
+                    else ((int*)e.okey[c])[pos] = (int)k.v[c];
+                    if (e.oknul[c]) e.oknul[c][pos] = (uint8_t)(k.nb >> c & 1);
+                }
+                const unsigned long long* st = t.st + s * t.slot_stride;
+                const unsigned long long seen =
+                    t.seen_mask ? st[t.n_aggs * t.word_stride] : 0ull;
+#pragma unroll
+                for (int a = 0; a < GPUE_GA_MAX_AGGS; a++) {
+                    if (a >= (int)t.n_aggs) break;
+                    const bool isnull = (t.seen_mask >> a & 1) && !(seen >> a & 1);
+                    e.oagg[a][pos] = isnull ? 0ll : (long long)st[a * t.word_stride];
+                    if (e.oanul[a]) e.oanul[a][pos] = isnull ? 1 : 0;
+                }
+            }
+        }
+        offset = wbase[BLOCK / WAVE];
+        __syncthreads();
+    }
+}
+
+struct gpue_group_agg {
+    gpue_session* s = nullptr;
+    int n_keys = 0, n_aggs = 0;
+    int32_t key_type[GPUE_GA_MAX_KEYS] = {}, key_nullable[GPUE_GA_MAX_KEYS] = {};
+    int32_t fn[GPUE_GA_MAX_AGGS] = {}, atype[GPUE_GA_MAX_AGGS] = {},
+            anullable[GPUE_GA_MAX_AGGS] = {};
+    GaTable d = {};
+    uint64_t groups = 0;                // settled groups (host copy of the claim counts)
+    uint32_t* claims = nullptr;         // slots claimed by the running sub-batch
+    uint64_t claims_cap = 0;
+    unsigned long long* ctl = nullptr;  // [0] claim count, [1] error latch, [2] emit cursor
+    bool aos = false;
+    int combine = 1; // 0 never, 1 for tables of at most GA_COMBINE_MAX_GROUPS groups, 2 always
+};
+
+static void ga_free_store(GaTable& d) {
+    (void)hipFree(d.slots);
+    (void)hipFree(d.kstore);
+    (void)hipFree(d.st);
+    d.slots = nullptr; d.kstore = nullptr; d.st = nullptr;
+}
+
+// allocate + initialise the arrays of `d` (layout fields already set) for cap slots
+static int ga_alloc_store(gpue_group_agg* t, GaTable& d, uint64_t cap) {
+    d.cap = cap;
+    d.slot_stride = t->aos ? d.n_words : 1;
+    d.word_stride = t->aos ? 1 : cap;
+    d.slots = nullptr; d.kstore = nullptr; d.st = nullptr;
+    hipError_t e = hipMalloc(&d.slots, cap * 8);
+    if (e == hipSuccess) e = hipMalloc(&d.kstore, cap * 8 * d.n_keys);
+    if (e == hipSuccess && d.n_words) e = hipMalloc(&d.st, cap * 8 * d.n_words);
+    if (e == hipSuccess) e = hipMemsetAsync(d.slots, 0, cap * 8, t->s->stream);
+    if (e != hipSuccess) {
+        ga_free_store(d);
+        snprintf(g_err, sizeof(g_err), "group_agg: table of %llu slots: %s",
+                 (unsigned long long)cap, hipGetErrorString(e));
+        return GPUE_ERR_HIP;
+    }
+    if (d.n_words) {
+        hipLaunchKernelGGL(k_ga_init, dim3(grid_for(cap * d.n_words)), dim3(BLOCK), 0,
+                           t->s->stream, d);
+        HIP_CHECK(hipGetLastError());
+    }
+    return GPUE_OK;
+}
+
+// the gpue_agg_table_ensure rule: load <= 5/8 even if all `additional` rows
+// are new groups; doubles + rehashes on device
+static int ga_ensure(gpue_group_agg* t, uint64_t additional) {
+    const uint64_t need = t->groups + additional;
+    if (need + need / 2 <= t->d.cap) return GPUE_OK;
+    uint64_t ncap = t->d.cap;
+    while (need + need / 2 > ncap) ncap <<= 1;
+    if (ncap > GA_MAX_CAP) {
+        snprintf(g_err, sizeof(g_err), "group_agg: %llu groups exceed the table limit",
+                 (unsigned long long)need);
+        return GPUE_ERR_ARG;
+    }
+    gpue_session* s = t->s;
+    GaTable nd = t->d;
+    int rc = ga_alloc_store(t, nd, ncap);
+    if (rc != GPUE_OK) return rc;
+    // small reads go through the session's pinned bounce buffer (~5 us, not ~20)
+    volatile unsigned long long* ctl = (volatile unsigned long long*)s->pinned;
+    hipLaunchKernelGGL(k_ga_rehash, dim3(grid_for(t->d.cap)), dim3(BLOCK), 0, s->stream,
+                       t->d, nd, t->ctl);
+    hipError_t e = hipMemcpyAsync(s->pinned, t->ctl, 16, hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess || ctl[1]) {
+        (void)hipMemsetAsync(t->ctl + 1, 0, 8, s->stream);
+        ga_free_store(nd);
+        snprintf(g_err, sizeof(g_err), "group_agg: rehash failed: %s",
+                 e != hipSuccess ? hipGetErrorString(e) : "new table full");
+        return GPUE_ERR_HIP;
+    }
+    ga_free_store(t->d);
+    t->d = nd;
+    return GPUE_OK;
+}
+
+int gpue_group_agg_create(gpue_session* s, const int32_t* key_type,
+                          const int32_t* key_nullable, int n_keys, const int32_t* agg_fn,
+                          const int32_t* agg_type, const int32_t* agg_nullable, int n_aggs,
+                          uint64_t capacity_hint, gpue_group_agg** out) {
+    ARG_CHECK(s && out && key_type && key_nullable);
+    ARG_CHECK(n_keys >= 1 && n_keys <= GPUE_GA_MAX_KEYS);
+    ARG_CHECK(n_aggs >= 0 && n_aggs <= GPUE_GA_MAX_AGGS);
+    ARG_CHECK(n_aggs == 0 || (agg_fn && agg_type && agg_nullable));
+    for (int k = 0; k < n_keys; k++)
+        ARG_CHECK(key_type[k] == GPUE_PT_I32 || key_type[k] == GPUE_PT_I64);
+    for (int a = 0; a < n_aggs; a++) {
+        ARG_CHECK(agg_fn[a] >= GPUE_GA_COUNT_STAR && agg_fn[a] <= GPUE_GA_MAX);
+        ARG_CHECK(agg_fn[a] == GPUE_GA_COUNT_STAR || agg_type[a] == GPUE_PT_I32 ||
+                  agg_type[a] == GPUE_PT_I64);
+    }
+    std::unique_ptr<gpue_group_agg> t(new gpue_group_agg());
+    t->s = s;
+    t->n_keys = n_keys;
+    t->n_aggs = n_aggs;
+    GaTable& d = t->d;
+    d.n_keys = n_keys;
+    d.n_aggs = n_aggs;
+    for (int k = 0; k < n_keys; k++) {
+        t->key_type[k] = key_type[k];
+        t->key_nullable[k] = key_nullable[k] != 0;
+    }
+    for (int a = 0; a < n_aggs; a++) {
+        t->fn[a] = agg_fn[a];
+        t->atype[a] = agg_fn[a] == GPUE_GA_COUNT_STAR ? GPUE_PT_I64 : agg_type[a];
+        t->anullable[a] = agg_nullable[a] != 0;
+        d.aop[a] = agg_fn[a] == GPUE_GA_COUNT_STAR ? GA_OP_ADD1
+                   : agg_fn[a] == GPUE_GA_COUNT    ? GA_OP_ADD1_NN
+                   : agg_fn[a] == GPUE_GA_SUM      ? GA_OP_ADDV
+                   : agg_fn[a] == GPUE_GA_MIN      ? GA_OP_MIN : GA_OP_MAX;
+        if (agg_fn[a] >= GPUE_GA_SUM && t->anullable[a]) d.seen_mask |= 1u << a;
+    }
+    d.n_words = n_aggs + (d.seen_mask ? 1 : 0);
+    // layout and pre-combine switches for experiments (tools/group_agg_bench.py);
+    // the defaults are the measured choices of DESIGN.md §4g
+    const char* lay = getenv("GPUE_GA_LAYOUT");
+    t->aos = lay && strcmp(lay, "aos") == 0;
+    const char* cmb = getenv("GPUE_GA_COMBINE");
+    if (cmb && cmb[0] >= '0' && cmb[0] <= '2' && !cmb[1]) t->combine = cmb[0] - '0';
+    uint64_t cap = 16;
+    while (cap < capacity_hint && cap < GA_MAX_CAP) cap <<= 1;
+    HIP_CHECK(hipSetDevice(s->device));
+    HIP_CHECK(hipMalloc(&t->ctl, 3 * 8));
+    HIP_CHECK(hipMemsetAsync(t->ctl, 0, 3 * 8, s->stream));
+    int rc = ga_alloc_store(t.get(), d, cap);
+    if (rc == GPUE_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = GPUE_ERR_HIP;
+    if (rc != GPUE_OK) {
+        gpue_group_agg_destroy(t.release());
+        return rc;
+    }
+    *out = t.release();
+    return GPUE_OK;
+}
+
+void gpue_group_agg_destroy(gpue_group_agg* t) {
+    if (!t) return;
+    ga_free_store(t->d);
+    (void)hipFree(t->claims);
+    (void)hipFree(t->ctl);
+    delete t;
+}
+
+int gpue_group_agg_reset(gpue_group_agg* t) {
+    ARG_CHECK(t);
+    HIP_CHECK(hipMemsetAsync(t->d.slots, 0, t->d.cap * 8, t->s->stream));
+    if (t->d.n_words) {
+        hipLaunchKernelGGL(k_ga_init, dim3(grid_for(t->d.cap * t->d.n_words)), dim3(BLOCK), 0,
+                           t->s->stream, t->d);
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipMemsetAsync(t->ctl, 0, 3 * 8, t->s->stream));
+    HIP_CHECK(hipStreamSynchronize(t->s->stream));
+    t->groups = 0;
+    return GPUE_OK;
+}
+
+int gpue_group_agg_size(gpue_session* s, gpue_group_agg* t, uint64_t* n_groups) {
+    ARG_CHECK(s && t && n_groups);
+    *n_groups = t->groups; // every push returns with its claims settled and counted
+    return GPUE_OK;
+}
+
+int gpue_group_agg_push(gpue_session* s, gpue_group_agg* t, gpue_dbuf** key_cols,
+                        gpue_dbuf** key_nulls, gpue_dbuf** agg_cols, gpue_dbuf** agg_nulls,
+                        uint64_t n_rows, int flags) {
+    ARG_CHECK(s && t && key_cols);
+    ARG_CHECK(flags == 0 || flags == GPUE_GA_MERGE);
+    ARG_CHECK(n_rows < (1ull << 32));
+    const bool merge = flags == GPUE_GA_MERGE;
+    GaInput in;
+    memset(&in, 0, sizeof(in));
+    uint32_t kw[GPUE_GA_MAX_KEYS] = {}, aw[GPUE_GA_MAX_AGGS] = {};
+    for (int k = 0; k < t->n_keys; k++) {
+        kw[k] = t->key_type[k] == GPUE_PT_I64 ? 8 : 4;
+        ARG_CHECK(key_cols[k] != nullptr);
+        ARG_CHECK(key_cols[k]->bytes >= n_rows * kw[k]);
+        gpue_dbuf* nl = key_nulls ? key_nulls[k] : nullptr;
+        if (nl) {
+            ARG_CHECK(t->key_nullable[k]); // null buffer for a key declared NOT NULL
+            ARG_CHECK(nl->bytes >= n_rows);
+        }
+        in.kcol[k] = key_cols[k]->ptr;
+        in.knul[k] = nl ? (const uint8_t*)nl->ptr : nullptr;
+        in.k64[k] = kw[k] == 8;
+    }
+    for (int a = 0; a < t->n_aggs; a++) {
+        in.aop[a] = t->d.aop[a];
+        if (t->fn[a] == GPUE_GA_COUNT_STAR && !merge) continue; // no input column
+        aw[a] = merge || t->atype[a] == GPUE_PT_I64 ? 8 : 4;
+        ARG_CHECK(agg_cols && agg_cols[a] != nullptr); // missing input column
+        ARG_CHECK(agg_cols[a]->bytes >= n_rows * aw[a]);
+        gpue_dbuf* nl = agg_nulls ? agg_nulls[a] : nullptr;
+        if (nl) {
+            ARG_CHECK(t->anullable[a]); // null buffer for an input declared NOT NULL
+            ARG_CHECK(nl->bytes >= n_rows);
+        }
+        in.acol[a] = agg_cols[a]->ptr;
+        in.anul[a] = nl ? (const uint8_t*)nl->ptr : nullptr;
+        in.a64[a] = aw[a] == 8;
+        // merge_batch: partial counts are added, NULL partials skipped
+        if (merge && in.aop[a] <= GA_OP_ADD1_NN) in.aop[a] = GA_OP_ADDV;
+    }
+    if (n_rows == 0) return GPUE_OK;
+    HIP_CHECK(hipSetDevice(s->device));
+    const uint64_t sub_max = std::min(n_rows, GA_SUB_BATCH);
+    if (t->claims_cap < sub_max) {
+        (void)hipFree(t->claims);
+        t->claims = nullptr;
+        t->claims_cap = 0;
+        HIP_CHECK(hipMalloc(&t->claims, sub_max * 4));
+        t->claims_cap = sub_max;
+    }
+    for (uint64_t base = 0; base < n_rows; base += GA_SUB_BATCH) {
+        const uint64_t n = std::min(GA_SUB_BATCH, n_rows - base);
+        int rc = ga_ensure(t, n);
+        if (rc != GPUE_OK) return rc;
+        GaInput sb = in;
+        for (int k = 0; k < t->n_keys; k++) {
+            sb.kcol[k] = (const char*)in.kcol[k] + base * kw[k];
+            if (in.knul[k]) sb.knul[k] = in.knul[k] + base;
+        }
+        for (int a = 0; a < t->n_aggs; a++) {
+            if (in.acol[a]) sb.acol[a] = (const char*)in.acol[a] + base * aw[a];
+            if (in.anul[a]) sb.anul[a] = in.anul[a] + base;
+        }
+        hipLaunchKernelGGL(k_ga_push, dim3(grid_for(n)), dim3(BLOCK), 0, s->stream, t->d, sb,
+                           n, t->claims, t->ctl, t->groups,
+                           t->combine == 2 ||
+                               (t->combine == 1 && t->groups >= 1 &&
+                                t->groups <= GA_COMBINE_MAX_GROUPS));
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(s->pinned, t->ctl, 16, hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        const volatile unsigned long long* ctl = (const volatile unsigned long long*)s->pinned;
+        const uint64_t claimed = ctl[0] - t->groups;
+        const bool full = ctl[1] != 0;
+        if (claimed) {
+            hipLaunchKernelGGL(k_ga_settle, dim3(grid_for(claimed)), dim3(BLOCK), 0, s->stream,
+                               t->d, sb, t->claims, claimed);
+            HIP_CHECK(hipGetLastError());
+            t->groups += claimed;
+        }
+        if (full) { // unreachable behind ga_ensure; the bounded walk's give-up code
+            HIP_CHECK(hipMemsetAsync(t->ctl + 1, 0, 8, s->stream));
+            HIP_CHECK(hipStreamSynchronize(s->stream));
+            snprintf(g_err, sizeof(g_err), "group_agg_push: hash table full");
+            return GPUE_ERR_HIP;
+        }
+    }
+    // the settle kernel reads the caller's key columns: done before we return
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GPUE_OK;
+}
+
+int gpue_group_agg_emit(gpue_session* s, gpue_group_agg* t, gpue_dbuf** out_keys,
+                        gpue_dbuf** out_key_nulls, gpue_dbuf** out_aggs,
+                        gpue_dbuf** out_agg_nulls, uint64_t max_out, uint64_t* n_groups) {
+    ARG_CHECK(s && t && out_keys && n_groups);
+    ARG_CHECK(t->n_aggs == 0 || out_aggs);
+    ARG_CHECK(max_out < (1ull << 32));
+    GaEmit e;
+    memset(&e, 0, sizeof(e));
+    const gpue_dbuf* wr[2 * (GPUE_GA_MAX_KEYS + GPUE_GA_MAX_AGGS)];
+    int n_wr = 0;
+    for (int k = 0; k < t->n_keys; k++) {
+        const uint32_t w = t->key_type[k] == GPUE_PT_I64 ? 8 : 4;
+        ARG_CHECK(out_keys[k] != nullptr);
+        ARG_CHECK(out_keys[k]->bytes >= max_out * w);
+        e.okey[k] = out_keys[k]->ptr;
+        e.k64[k] = w == 8;
+        wr[n_wr++] = out_keys[k];
+        if (t->key_nullable[k]) {
+            ARG_CHECK(out_key_nulls && out_key_nulls[k] != nullptr);
+            ARG_CHECK(out_key_nulls[k]->bytes >= max_out);
+            e.oknul[k] = (uint8_t*)out_key_nulls[k]->ptr;
+            wr[n_wr++] = out_key_nulls[k];
+        }
+    }
+    for (int a = 0; a < t->n_aggs; a++) {
+        ARG_CHECK(out_aggs[a] != nullptr);
+        ARG_CHECK(out_aggs[a]->bytes >= max_out * 8);
+        e.oagg[a] = (long long*)out_aggs[a]->ptr;
+        wr[n_wr++] = out_aggs[a];
+        if (t->d.seen_mask >> a & 1) {
+            ARG_CHECK(out_agg_nulls && out_agg_nulls[a] != nullptr);
+            ARG_CHECK(out_agg_nulls[a]->bytes >= max_out);
+            e.oanul[a] = (uint8_t*)out_agg_nulls[a]->ptr;
+            wr[n_wr++] = out_agg_nulls[a];
+        }
+    }
+    for (int x = 0; x < n_wr; x++)
+        for (int y = x + 1; y < n_wr; y++) {
+            const char *xa = (const char*)wr[x]->ptr, *ya = (const char*)wr[y]->ptr;
+            ARG_CHECK(!(xa < ya + wr[y]->bytes && ya < xa + wr[x]->bytes)); // outputs overlap
+        }
+    *n_groups = t->groups;
+    if (t->groups > max_out) {
+        snprintf(g_err, sizeof(g_err), "group_agg_emit: %llu groups exceed max_out %llu",
+                 (unsigned long long)t->groups, (unsigned long long)max_out);
+        return GPUE_ERR_ARG;
+    }
+    if (t->groups == 0) return GPUE_OK;
+    HIP_CHECK(hipSetDevice(s->device));
+    HIP_CHECK(hipMemsetAsync(t->ctl + 2, 0, 8, s->stream));
+    hipLaunchKernelGGL(k_ga_emit, dim3(grid_for(t->d.cap)), dim3(BLOCK), 0, s->stream, t->d, e,
+                       max_out, t->ctl + 2);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GPUE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Config 5 — TPC-H Q3-shaped: lineitem ⋈ orders ⋈ customer with a 16-byte
 // dictionary-string filter (SERIALIZED_FIXED_SIZE_LARGEINT packing: two u64
 // compares — reference join_hash_table.cpp:185-192), decimal revenue as

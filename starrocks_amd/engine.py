@@ -200,6 +200,15 @@ def _declare(lib):
                                                  ctypes.POINTER(c_u64)]),
         "gpue_hash_agg_emit_u64": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u64,
                                            ctypes.POINTER(c_u64)]),
+        "gpue_group_agg_create": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32,
+                                          c_u64, ctypes.POINTER(c_vp)]),
+        "gpue_group_agg_push": (c_i32, [c_vp, c_vp] + [ctypes.POINTER(c_vp)] * 4 +
+                                [c_u64, c_i32]),
+        "gpue_group_agg_size": (c_i32, [c_vp, c_vp, ctypes.POINTER(c_u64)]),
+        "gpue_group_agg_emit": (c_i32, [c_vp, c_vp] + [ctypes.POINTER(c_vp)] * 4 +
+                                [c_u64, ctypes.POINTER(c_u64)]),
+        "gpue_group_agg_reset": (c_i32, [c_vp]),
+        "gpue_group_agg_destroy": (None, [c_vp]),
         "gpue_sbf_build_i32": (c_i32, [c_vp, c_vp, c_u64, c_i32, c_vp]),
         "gpue_sbf_test_i32": (c_i32, [c_vp, c_vp, c_u64, c_vp, c_i32, c_vp]),
         "gpue_topk_i64": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_i32, c_vp, c_vp]),
@@ -299,6 +308,16 @@ class AsofTable:
         if self._h:
             self._lib.gpue_asof_table_destroy(self._h)
             self._h = None
+
+
+class GroupAgg:
+    """A general GROUP BY table (gpue_group_agg): the handle plus the layout
+    it was created with (a groupagg.GroupAggSpec)."""
+
+    def __init__(self, eng: "Engine", handle, spec):
+        self._lib = eng._lib
+        self._h = handle
+        self.spec = spec
 
 
 class Engine:
@@ -946,6 +965,114 @@ class Engine:
             self._h, keys._h, vals._h, n, capacity_hint, out_keys._h, out_lo._h,
             out_hi._h, max_out, ctypes.byref(g)))
         return g.value
+
+    # --- general GROUP BY (gpue.h "general GROUP BY") ---
+    GA_COUNT_STAR, GA_COUNT, GA_SUM, GA_MIN, GA_MAX = range(5)
+
+    @staticmethod
+    def _vp_array(items, n):
+        return (c_vp * max(n, 1))(*[None if b is None else b._h for b in items])
+
+    def group_agg_create(self, key_types, key_nullable, agg_fns=(), agg_types=(),
+                         agg_nullable=(), capacity_hint=0) -> GroupAgg:
+        """A persistent, growable GROUP BY table over len(key_types) key
+        columns (PT_I32 / PT_I64) and len(agg_fns) aggregates (GA_*); the
+        layout is fixed here. capacity_hint is only a starting size."""
+        i32 = lambda xs: np.ascontiguousarray([int(x) for x in xs], np.int32)
+        kt, kn = i32(key_types), i32(key_nullable)
+        af, at, an = i32(agg_fns), i32(agg_types), i32(agg_nullable)
+        h = c_vp()
+        _ck(self._lib, self._lib.gpue_group_agg_create(
+            self._h, kt.ctypes.data_as(c_vp), kn.ctypes.data_as(c_vp), len(kt),
+            af.ctypes.data_as(c_vp), at.ctypes.data_as(c_vp), an.ctypes.data_as(c_vp),
+            len(af), capacity_hint, ctypes.byref(h)))
+        from starrocks_amd.groupagg import GroupAggSpec
+        return GroupAgg(self, h, GroupAggSpec(key_types, key_nullable, agg_fns, agg_types,
+                                              agg_nullable))
+
+    def group_agg_push(self, ga: GroupAgg, keys, aggs, n_rows, merge=False):
+        """keys = [(DBuf, nulls DBuf or None)], aggs = [(DBuf or None, nulls
+        DBuf or None)] in the table's layout. merge=True: the aggregate
+        inputs are int64 partial states (COUNT_STAR has one too)."""
+        nk, na = len(keys), len(aggs)
+        _ck(self._lib, self._lib.gpue_group_agg_push(
+            self._h, ga._h, self._vp_array([k[0] for k in keys], nk),
+            self._vp_array([k[1] for k in keys], nk),
+            self._vp_array([a[0] for a in aggs], na),
+            self._vp_array([a[1] for a in aggs], na), n_rows, 1 if merge else 0))
+
+    def group_agg_size(self, ga: GroupAgg) -> int:
+        g = c_u64()
+        _ck(self._lib, self._lib.gpue_group_agg_size(self._h, ga._h, ctypes.byref(g)))
+        return g.value
+
+    def group_agg_emit(self, ga: GroupAgg, out_keys, out_aggs, max_out) -> int:
+        """out_keys / out_aggs = [(DBuf, nulls DBuf or None)]; the table stays
+        usable. Returns the group count."""
+        nk, na = len(out_keys), len(out_aggs)
+        g = c_u64()
+        _ck(self._lib, self._lib.gpue_group_agg_emit(
+            self._h, ga._h, self._vp_array([k[0] for k in out_keys], nk),
+            self._vp_array([k[1] for k in out_keys], nk),
+            self._vp_array([a[0] for a in out_aggs], na),
+            self._vp_array([a[1] for a in out_aggs], na), max_out, ctypes.byref(g)))
+        return g.value
+
+    def group_agg_reset(self, ga: GroupAgg):
+        _ck(self._lib, self._lib.gpue_group_agg_reset(ga._h))
+
+    def group_agg_destroy(self, ga: GroupAgg):
+        if ga._h:
+            self._lib.gpue_group_agg_destroy(ga._h)
+            ga._h = None
+
+    def group_agg_emit_alloc(self, ga: GroupAgg):
+        """Emit into exact-size outputs allocated from size(): null buffers
+        only where the key / output is nullable; all freed on any exception.
+        Returns (n_groups, [(values, nulls or None)] per key, same per agg)."""
+        spec = ga.spec
+        g = self.group_agg_size(ga)
+        bufs = []
+
+        def pair(width, nullable):
+            bufs.append(self.alloc(max(g * width, 1)))
+            bufs.append(self.alloc(max(g, 1)) if nullable else None)
+            return bufs[-2], bufs[-1]
+
+        try:
+            out_keys = [pair(spec.key_width(k), spec.key_nullable[k])
+                        for k in range(spec.n_keys)]
+            out_aggs = [pair(8, nl) for nl in spec.out_nullable]
+            got = self.group_agg_emit(ga, out_keys, out_aggs, g)
+            assert got == g
+        except BaseException:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+            raise
+        return g, out_keys, out_aggs
+
+    def group_agg(self, keys, aggs, n_rows, capacity_hint=0, merge=False):
+        """One-shot GROUP BY: keys = [(DBuf, nulls DBuf or None, PT_I32 /
+        PT_I64)], aggs = [(GA_* fn, DBuf or None, nulls DBuf or None, type)],
+        the tuple style of project(); a key / input is nullable iff it has a
+        null buffer. Validates (ValueError), builds the table, pushes the
+        n_rows rows, emits into exact-size outputs and drops the table.
+        Returns (n_groups, [(values, nulls or None)] per key, same per agg);
+        the inputs are left alone."""
+        from starrocks_amd.groupagg import GroupAggSpec
+        spec = GroupAggSpec.of(keys, aggs)
+        spec.check_push([(k[0], k[1]) for k in keys], [(a[1], a[2]) for a in aggs],
+                        n_rows, 1 if merge else 0)
+        ga = self.group_agg_create(spec.key_types, spec.key_nullable, spec.agg_fns,
+                                   spec.agg_types, spec.agg_nullable,
+                                   capacity_hint or min(2 * n_rows, 1 << 21))
+        try:
+            self.group_agg_push(ga, [(k[0], k[1]) for k in keys],
+                                [(a[1], a[2]) for a in aggs], n_rows, merge)
+            return self.group_agg_emit_alloc(ga)
+        finally:
+            self.group_agg_destroy(ga)
 
     def graph_capture(self, fn):
         """Capture fn()'s async launches as a hipGraph; returns the exec

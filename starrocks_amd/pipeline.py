@@ -688,6 +688,96 @@ class ProjectOperator(Operator):
         return c
 
 
+class GroupAggSinkOperator(Operator):
+    """GROUP BY as a blocking sink — the AggregateBlockingSinkOperator over
+    Aggregator::compute_agg_states + update_batch (merge_batch with
+    merge=True), for any key tuple and aggregate list the general table takes
+    (starrocks_amd/groupagg.py).
+
+    Chunks are {"n": rows, "cols": [DBuf, ...]}. key_map[i] = (chunk column
+    index, chunk column index of its u8 null mask or None, type 0 int32 / 1
+    int64) binds key i, as ProjectOperator's col_map; agg_map[j] = (function
+    COUNT_STAR / COUNT / SUM / MIN / MAX or its lower-case name, chunk column
+    index or None for COUNT_STAR, null mask column index or None, type) binds
+    aggregate j. A key or input is nullable iff it names a null mask column.
+    With merge=True every aggregate input is an int64 partial state as a
+    partial GROUP BY emitted it, COUNT_STAR included.
+
+    Per pushed chunk: one push into the table (which grows as it needs to);
+    every chunk column is freed. result() emits into exact-size outputs,
+    drops the table and returns (n_groups, [(values, nulls or None)] per key,
+    the same per aggregate) as numpy arrays, key-sorted (groupagg.sort_result).
+
+    Uses only engine.group_agg_create / group_agg_push / group_agg_emit_alloc
+    / group_agg_destroy and DBuf.d2h / free, so it runs against a numpy
+    stand-in engine without a GPU."""
+
+    def __init__(self, engine, key_map, agg_map, merge=False, capacity_hint=0):
+        super().__init__()
+        from starrocks_amd.groupagg import FN_NAMES, GroupAggSpec
+        self._e = engine
+        self._keys = [(int(c), None if nl is None else int(nl), t) for c, nl, t in key_map]
+        self._aggs = [(FN_NAMES.get(f, f) if isinstance(f, str) else f,
+                       None if c is None else int(c), None if nl is None else int(nl), t)
+                      for f, c, nl, t in agg_map]
+        self._merge = bool(merge)
+        self.spec = GroupAggSpec([t for _, _, t in self._keys],
+                                 [nl is not None for _, nl, _ in self._keys],
+                                 [f for f, _, _, _ in self._aggs],
+                                 [t for _, _, _, t in self._aggs],
+                                 [nl is not None for _, _, nl, _ in self._aggs])
+        for a, (_, c, _, _) in enumerate(self._aggs):
+            if c is None and self.spec.needs_input(a, self._merge):
+                raise ValueError(f"aggregate {a} needs an input column")
+        idx = [c for c, _, _ in self._keys] + [nl for _, nl, _ in self._keys] + \
+              [c for _, c, _, _ in self._aggs] + [nl for _, _, nl, _ in self._aggs]
+        if any(i is not None and i < 0 for i in idx):
+            raise ValueError("chunk column indexes must be non-negative")
+        self._ga = engine.group_agg_create(self.spec.key_types, self.spec.key_nullable,
+                                           self.spec.agg_fns, self.spec.agg_types,
+                                           self.spec.agg_nullable, capacity_hint)
+        self.rows = 0
+
+    def need_input(self):
+        return not self._finishing
+
+    def has_output(self):
+        return False
+
+    def push_chunk(self, chunk):
+        n, cols = chunk["n"], chunk["cols"]
+        col = lambda i: None if i is None else cols[i]
+        try:
+            if n:
+                self._e.group_agg_push(
+                    self._ga, [(cols[c], col(nl)) for c, nl, _ in self._keys],
+                    [(col(c) if self.spec.needs_input(a, self._merge) else None, col(nl))
+                     for a, (_, c, nl, _) in enumerate(self._aggs)], n, self._merge)
+        finally:
+            for b in cols:
+                b.free()
+        self.rows += n
+
+    def result(self):
+        from starrocks_amd.groupagg import _DT, sort_result
+        g, keys, aggs = self._e.group_agg_emit_alloc(self._ga)
+        try:
+            pull = lambda b, dt: np.empty(0, dt) if g == 0 else b.d2h(dt, g)
+            hk = [(pull(v, _DT[t]), None if nl is None else pull(nl, np.uint8))
+                  for (v, nl), t in zip(keys, self.spec.key_types)]
+            ha = [(pull(v, np.int64), None if nl is None else pull(nl, np.uint8))
+                  for v, nl in aggs]
+        finally:
+            for v, nl in keys + aggs:
+                v.free()
+                if nl is not None:
+                    nl.free()
+            self._e.group_agg_destroy(self._ga)
+            self._ga = None
+        hk, ha = sort_result(hk, ha)
+        return g, hk, ha
+
+
 def q1_operator_pipeline(engine, seed, total_rows, year=1993,
                          chunk_rows=DEFAULT_CHUNK_ROWS, dim_chunk_rows=1000):
     """Config-2's plan as the reference would run it — dim source -> build
