@@ -1007,6 +1007,109 @@ int gpue_asof_probe_emit_nulls_i32(gpue_session* s, gpue_asof_table* t,
                                    uint64_t* match_count);
 int gpue_asof_table_destroy(gpue_asof_table* t);
 
+/* ---- window functions: fn(...) OVER (PARTITION BY ... ORDER BY ... frame) --
+ * The analytic operator (reference exec/analytor.cpp, exec/pipeline/analysis/):
+ * one call evaluates 1..GPUE_WIN_MAX_FUNCS window functions that share one
+ * PARTITION BY / ORDER BY clause. The entry does not sort: order_idx is a u32
+ * permutation of [0, n_rows) listing the rows sorted by (partition keys, order
+ * keys), exactly as gpue_topn writes it when called with the partition keys in
+ * front of the order keys and limit >= n_rows; NULL = the rows are already in
+ * that order. The buffer is trusted to be a permutation, but an index
+ * >= n_rows is never dereferenced: the boundary pass latches the session's
+ * device error word and the call returns GPUE_ERR_ARG with nothing else run.
+ *
+ * Keys: 0..GPUE_WIN_MAX_KEYS partition and 0..GPUE_WIN_MAX_KEYS order columns,
+ * GPUE_PT_I32 / GPUE_PT_I64, with the nullable conventions of
+ * gpue_group_agg_push (declared nullability + optional u8 null column). They
+ * are used for equality only: sorted position i starts a partition iff i == 0
+ * or some partition key differs from position i-1, and starts a peer group iff
+ * it starts a partition or some order key differs. NULL equals NULL, the cell
+ * under a NULL is never read, every 64-bit pattern is a legal key. No
+ * partition keys: one partition. No order keys: all rows of a partition are
+ * peers.
+ *
+ * Functions (all outputs int64; part_start/part_end/peer_start/peer_end are
+ * sorted positions, inclusive; i is the row's sorted position):
+ *   ROW_NUMBER  i - part_start + 1          RANK  peer_start - part_start + 1
+ *   DENSE_RANK  peer groups in [part_start, i]
+ *   NTILE       param0 = B >= 1; size = part_end - part_start + 1, q = size / B,
+ *               r = size % B, rn0 = i - part_start: rn0/(q+1) + 1 if
+ *               rn0 < r*(q+1), else r + (rn0 - r*(q+1))/q + 1
+ *   COUNT_STAR, COUNT, SUM, MIN, MAX   aggregate over the frame [lo, hi]: COUNT
+ *               counts non-NULL inputs, SUM wraps mod 2^64 (as GPUE_GA_SUM),
+ *               SUM / MIN / MAX skip NULLs and are NULL when the frame holds
+ *               no non-NULL input
+ *   FIRST_VALUE, LAST_VALUE   the input at lo / at hi, a NULL passed through
+ *   LAG, LEAD   param0 = k >= 0: the input at i - k / i + k if that position is
+ *               inside the partition, else param1 if has_default, else NULL
+ * Frames: GPUE_WF_ROWS: lo = max(part_start, i - frame_lo) (part_start when
+ * GPUE_WIN_UNBOUNDED), hi = min(part_end, i + frame_hi) (part_end when
+ * unbounded), frame_lo / frame_hi >= 0. GPUE_WF_RANGE: frame_lo must be
+ * unbounded, frame_hi is 0 (hi = peer_end, SQL's default frame under ORDER BY)
+ * or unbounded. MIN / MAX need frame_lo unbounded (no sliding minimum). The
+ * frame fields are ignored for the ranking functions, NTILE and LAG / LEAD;
+ * the input fields are ignored for functions that take no input.
+ *
+ * Output nullability is static: never for the ranking functions, NTILE,
+ * COUNT_STAR, COUNT; iff the input was declared nullable for SUM, MIN, MAX,
+ * FIRST_VALUE, LAST_VALUE; LAG / LEAD always, unless has_default is set and
+ * the input is not nullable. A NULL output stores value 0, null byte 1,
+ * otherwise null byte 0. A nullable output needs its null column; the null
+ * column of a non-nullable output is ignored. The result for sorted position
+ * i is written at out[order_idx[i]] (it lines up with the input columns), or
+ * at out[i] with GPUE_WIN_OUT_SORTED.
+ *
+ * Scratch, allocated and freed inside the call, in bytes for n = n_rows:
+ * n (boundary flags) + 8 n (part_start, peer_start) + 8 n more (part_end,
+ * peer_end) unless every function is ROW_NUMBER / RANK / DENSE_RANK / LAG /
+ * FIRST_VALUE, + per function: SUM 8 n, MIN / MAX 8 n, each + 4 n when its
+ * input comes with a null column; COUNT 4 n when its input comes with a null
+ * column; DENSE_RANK 4 n; the others 0; + 16 bytes per scan tile
+ * (GPUE_WIN_TILE rows).
+ *
+ * GPUE_ERR_ARG, before any launch or allocation, for: n_part / n_order outside
+ * 0..GPUE_WIN_MAX_KEYS, n_funcs outside 1..GPUE_WIN_MAX_FUNCS, an unknown
+ * type, function, frame mode or flag, an illegal frame, NTILE with B < 1, a
+ * negative k, n_rows >= 2^32, any buffer shorter than n_rows elements, a
+ * missing input or output column, a missing null column for a nullable output,
+ * a null buffer for a column declared non-nullable, an output that overlaps
+ * another output or an input. n_rows == 0 returns GPUE_OK. Out of scope:
+ * sliding MIN / MAX, RANGE with numeric offsets, IGNORE NULLS, CUME_DIST /
+ * PERCENT_RANK, frames that exclude the current row. */
+#define GPUE_WIN_MAX_FUNCS 8
+#define GPUE_WIN_MAX_KEYS 4
+#define GPUE_WIN_TILE 2048        /* rows per scan tile */
+#define GPUE_WIN_MID 1024         /* tile aggregates per sweep of the middle pass */
+#define GPUE_WFN_ROW_NUMBER 0
+#define GPUE_WFN_RANK 1
+#define GPUE_WFN_DENSE_RANK 2
+#define GPUE_WFN_NTILE 3
+#define GPUE_WFN_COUNT_STAR 4
+#define GPUE_WFN_COUNT 5
+#define GPUE_WFN_SUM 6
+#define GPUE_WFN_MIN 7
+#define GPUE_WFN_MAX 8
+#define GPUE_WFN_FIRST_VALUE 9
+#define GPUE_WFN_LAST_VALUE 10
+#define GPUE_WFN_LAG 11
+#define GPUE_WFN_LEAD 12
+#define GPUE_WF_ROWS 0
+#define GPUE_WF_RANGE 1
+#define GPUE_WIN_UNBOUNDED (-1)   /* frame_lo / frame_hi */
+#define GPUE_WIN_OUT_SORTED 1     /* flag: write the result of sorted position i at out[i] */
+int gpue_window_eval(gpue_session* s, uint64_t n_rows, gpue_dbuf* order_idx /* u32 or NULL */,
+                     gpue_dbuf** part_cols, gpue_dbuf** part_nulls, const int32_t* part_type,
+                     const int32_t* part_nullable, int n_part,
+                     gpue_dbuf** order_cols, gpue_dbuf** order_nulls, const int32_t* order_type,
+                     const int32_t* order_nullable, int n_order,
+                     const int32_t* fn /* GPUE_WFN_* */, gpue_dbuf** in_cols,
+                     gpue_dbuf** in_nulls, const int32_t* in_type /* GPUE_PT_* */,
+                     const int32_t* in_nullable, const int32_t* frame_mode,
+                     const int64_t* frame_lo, const int64_t* frame_hi, const int64_t* param0,
+                     const int64_t* param1, const int32_t* has_default, int n_funcs,
+                     gpue_dbuf** out_cols /* int64 */, gpue_dbuf** out_nulls /* u8 */,
+                     int flags);
+
 /* ---- event timing on the session stream (bench roofline evidence) ---- */
 int gpue_timer_start(gpue_session* s);
 int gpue_timer_stop(gpue_session* s, float* ms_out);

@@ -11433,3 +11433,654 @@ int gpue_asof_table_destroy(gpue_asof_table* t) {
     delete t;
     return GPUE_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Window functions (gpue_window_eval): device-wide scans over the sorted order
+// plus one gather-and-finish pass. DESIGN.md §4h.
+//
+// One scan skeleton, templated on the operator (Op::T, identity, combine),
+// a source functor (item at scan position p) and a sink functor. A tile is
+// WS_TILE rows: 256 threads x WS_ITEMS rows each, laid out so that a wave's
+// every load / store instruction covers one contiguous run (ws_pos) — serial
+// scan of a lane's consecutive rows, wave scan of the lane totals with
+// cross-lane shuffles group after group, the four wave totals through LDS.
+// Device-wide it is reduce / scan-the-tile-aggregates
+// / apply in three launches (the count / scan / emit structure of
+// gpue_mask_compact): no workgroup waits on another workgroup's store, and
+// the second read of the input is the accepted price. Backward scans are
+// forward scans whose functors map position p to row n-1-p.
+// ---------------------------------------------------------------------------
+static constexpr int WS_ITEMS = 8;
+static constexpr int WS_TILE = BLOCK * WS_ITEMS;          // 2048 rows
+static constexpr int WS_MID_ITEMS = 4;
+static constexpr int WS_MID = BLOCK * WS_MID_ITEMS;       // 1024 tile aggregates per sweep
+static_assert(WS_TILE == GPUE_WIN_TILE && WS_MID == GPUE_WIN_MID, "header states the geometry");
+#define AGG_ERR_WIN_IDX 4u
+
+__device__ static __forceinline__ uint32_t ws_up(uint32_t v, int off) { return __shfl_up(v, off, WAVE); }
+__device__ static __forceinline__ uint64_t ws_up(uint64_t v, int off) {
+    return (uint64_t)__shfl_up((unsigned long long)v, off, WAVE);
+}
+__device__ static __forceinline__ uint2 ws_up(uint2 v, int off) {
+    return make_uint2(__shfl_up(v.x, off, WAVE), __shfl_up(v.y, off, WAVE));
+}
+// running MIN / MAX state: "has no value yet" is a flag, never the identity
+// element (I64_MAX / I64_MIN are real inputs); v is 0 while !has
+struct WsSeg {
+    int64_t v;
+    uint32_t fl; // bit 0: has a value, bit 1: a segment (partition) starts in the run
+};
+__device__ static __forceinline__ WsSeg ws_up(WsSeg a, int off) {
+    WsSeg r;
+    r.v = (int64_t)__shfl_up((unsigned long long)a.v, off, WAVE);
+    r.fl = __shfl_up(a.fl, off, WAVE);
+    return r;
+}
+// the last lane's value, to every lane
+__device__ static __forceinline__ uint32_t ws_last(uint32_t v) { return __shfl(v, WAVE - 1, WAVE); }
+__device__ static __forceinline__ uint64_t ws_last(uint64_t v) {
+    return (uint64_t)__shfl((unsigned long long)v, WAVE - 1, WAVE);
+}
+__device__ static __forceinline__ uint2 ws_last(uint2 v) {
+    return make_uint2(__shfl(v.x, WAVE - 1, WAVE), __shfl(v.y, WAVE - 1, WAVE));
+}
+__device__ static __forceinline__ WsSeg ws_last(WsSeg a) {
+    WsSeg r;
+    r.v = (int64_t)__shfl((unsigned long long)a.v, WAVE - 1, WAVE);
+    r.fl = __shfl(a.fl, WAVE - 1, WAVE);
+    return r;
+}
+
+// Op::V = consecutive rows a lane holds per group (ws_pos): 16 bytes of the
+// widest array the scan streams, so each of its load / store instructions
+// covers one contiguous run per wave
+struct WsMax2 { // forward max-scan of "position if flagged", partitions and peers at once
+    using T = uint2;
+    static constexpr int V = 4;
+    __device__ static T identity() { return make_uint2(0u, 0u); }
+    __device__ static T combine(T a, T b) { return make_uint2(max(a.x, b.x), max(a.y, b.y)); }
+};
+struct WsAdd64 {
+    using T = uint64_t;
+    static constexpr int V = 2;
+    __device__ static T identity() { return 0; }
+    __device__ static T combine(T a, T b) { return a + b; }
+};
+struct WsAdd32 {
+    using T = uint32_t;
+    static constexpr int V = 4;
+    __device__ static T identity() { return 0; }
+    __device__ static T combine(T a, T b) { return a + b; }
+};
+template <bool IS_MAX>
+struct WsSegExt { // segmented running MIN / MAX: b restarts the run where it holds a segment start
+    using T = WsSeg;
+    static constexpr int V = 2;
+    __device__ static T identity() { return WsSeg{0, 0u}; }
+    __device__ static T combine(T a, T b) {
+        if (b.fl & 2u) return b;
+        T r;
+        r.fl = a.fl | b.fl;
+        const bool ha = a.fl & 1u, hb = b.fl & 1u;
+        const int64_t m = IS_MAX ? (a.v > b.v ? a.v : b.v) : (a.v < b.v ? a.v : b.v);
+        r.v = ha && hb ? m : (ha ? a.v : b.v);
+        return r;
+    }
+};
+
+// Where item j of a thread sits in its tile: a wave owns 64 * ITEMS consecutive
+// rows as ITEMS / V groups of 64 * V rows, and a lane V consecutive rows of
+// each group. Scan order = row order: group, then lane, then row in the lane.
+template <int ITEMS, int V>
+__device__ static __forceinline__ uint32_t ws_pos(int j) {
+    const uint32_t lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    return wid * (WAVE * ITEMS) + (j / V) * (WAVE * V) + lane * V + (j % V);
+}
+
+// Inclusive scan of a tile held as ws_pos lays it out, `carry` combined in
+// front; returns carry + the whole tile. lds: BLOCK / WAVE entries.
+template <typename Op, int ITEMS>
+__device__ static __forceinline__ typename Op::T
+ws_block_scan(typename Op::T (&x)[ITEMS], typename Op::T carry, typename Op::T* lds) {
+    using T = typename Op::T;
+    constexpr int V = Op::V, G = ITEMS / V;
+    static_assert(G >= 1 && G * V == ITEMS, "items per lane are whole groups");
+    const int lane = threadIdx.x & (WAVE - 1), wid = threadIdx.x / WAVE;
+    T excl[G];            // what precedes the lane's rows of group g inside the wave
+    T run = Op::identity(); // the wave's groups so far (the same in every lane)
+    #pragma unroll
+    for (int g = 0; g < G; g++) {
+        #pragma unroll
+        for (int e = 1; e < V; e++) x[g * V + e] = Op::combine(x[g * V + e - 1], x[g * V + e]);
+        T inc = x[g * V + V - 1];
+        #pragma unroll
+        for (int off = 1; off < WAVE; off <<= 1) {
+            T o = ws_up(inc, off);
+            if (lane >= off) inc = Op::combine(o, inc);
+        }
+        const T up = ws_up(inc, 1);
+        excl[g] = lane == 0 ? run : Op::combine(run, up);
+        run = Op::combine(run, ws_last(inc));
+    }
+    if (lane == WAVE - 1) lds[wid] = run;
+    __syncthreads();
+    T pre = carry, all = carry;
+    #pragma unroll
+    for (int w = 0; w < BLOCK / WAVE; w++) {
+        const T t = lds[w];
+        if (w < wid) pre = Op::combine(pre, t);
+        all = Op::combine(all, t);
+    }
+    #pragma unroll
+    for (int g = 0; g < G; g++) {
+        const T front = Op::combine(pre, excl[g]);
+        #pragma unroll
+        for (int e = 0; e < V; e++) x[g * V + e] = Op::combine(front, x[g * V + e]);
+    }
+    __syncthreads(); // lds is reused by the caller's next tile
+    return all;
+}
+
+template <typename Op, typename Src, int ITEMS>
+__device__ static __forceinline__ void
+ws_load_tile(const Src& src, uint64_t base, uint64_t n, typename Op::T (&x)[ITEMS]) {
+    if (base + (uint64_t)BLOCK * ITEMS <= n) { // whole tile: no per-item bound
+        #pragma unroll
+        for (int j = 0; j < ITEMS; j++)
+            x[j] = src.load((uint32_t)(base + ws_pos<ITEMS, Op::V>(j)));
+    } else {
+        #pragma unroll
+        for (int j = 0; j < ITEMS; j++) {
+            const uint64_t p = base + ws_pos<ITEMS, Op::V>(j);
+            x[j] = p < n ? src.load((uint32_t)p) : Op::identity();
+        }
+    }
+}
+
+// reduce: one aggregate per tile
+template <typename Op, typename Src>
+__global__ __launch_bounds__(BLOCK) void
+k_ws_reduce(const Src src, uint64_t n, uint32_t n_tiles, typename Op::T* __restrict__ tile_agg) {
+    using T = typename Op::T;
+    __shared__ T lds[BLOCK / WAVE];
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        T x[WS_ITEMS];
+        ws_load_tile<Op>(src, (uint64_t)t * WS_TILE, n, x);
+        const T all = ws_block_scan<Op>(x, Op::identity(), lds);
+        if (threadIdx.x == 0) tile_agg[t] = all;
+    }
+}
+
+// scan the tile aggregates in place (inclusive): one block, WS_MID aggregates
+// per sweep, the carry rides from sweep to sweep
+template <typename Op>
+__global__ __launch_bounds__(BLOCK) void
+k_ws_mid(typename Op::T* __restrict__ tile_agg, uint32_t n_tiles) {
+    using T = typename Op::T;
+    __shared__ T lds[BLOCK / WAVE];
+    T carry = Op::identity();
+    for (uint64_t base = 0; base < n_tiles; base += WS_MID) {
+        T x[WS_MID_ITEMS];
+        #pragma unroll
+        for (int j = 0; j < WS_MID_ITEMS; j++) {
+            const uint64_t p = base + ws_pos<WS_MID_ITEMS, Op::V>(j);
+            x[j] = p < n_tiles ? tile_agg[p] : Op::identity();
+        }
+        carry = ws_block_scan<Op>(x, carry, lds);
+        #pragma unroll
+        for (int j = 0; j < WS_MID_ITEMS; j++) {
+            const uint64_t p = base + ws_pos<WS_MID_ITEMS, Op::V>(j);
+            if (p < n_tiles) tile_agg[p] = x[j];
+        }
+    }
+}
+
+// apply: rescan each tile behind its prefix and hand every row to the sink
+template <typename Op, typename Src, typename Dst>
+__global__ __launch_bounds__(BLOCK) void
+k_ws_apply(const Src src, const Dst dst, uint64_t n, uint32_t n_tiles,
+           const typename Op::T* __restrict__ tile_incl) {
+    using T = typename Op::T;
+    __shared__ T lds[BLOCK / WAVE];
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t base = (uint64_t)t * WS_TILE;
+        T x[WS_ITEMS];
+        ws_load_tile<Op>(src, base, n, x);
+        ws_block_scan<Op>(x, t ? tile_incl[t - 1] : Op::identity(), lds);
+        if (base + WS_TILE <= n) { // whole tile: unconditional, mergeable stores
+            #pragma unroll
+            for (int j = 0; j < WS_ITEMS; j++)
+                dst.store((uint32_t)(base + ws_pos<WS_ITEMS, Op::V>(j)), x[j]);
+        } else {
+            #pragma unroll
+            for (int j = 0; j < WS_ITEMS; j++) {
+                const uint64_t p = base + ws_pos<WS_ITEMS, Op::V>(j);
+                if (p < n) dst.store((uint32_t)p, x[j]);
+            }
+        }
+    }
+}
+
+template <typename Op, typename Src, typename Dst>
+static void ws_scan(gpue_session* s, const Src& src, const Dst& dst, uint64_t n,
+                    uint32_t n_tiles, void* tile_agg) {
+    using T = typename Op::T;
+    const uint32_t nb = (uint32_t)std::min<uint64_t>(n_tiles, MAX_GRID);
+    if (n_tiles > 1) { // a single tile has nothing in front of it
+        hipLaunchKernelGGL((k_ws_reduce<Op, Src>), dim3(nb), dim3(BLOCK), 0, s->stream, src, n,
+                           n_tiles, (T*)tile_agg);
+        hipLaunchKernelGGL((k_ws_mid<Op>), dim3(1), dim3(BLOCK), 0, s->stream, (T*)tile_agg,
+                           n_tiles);
+    }
+    hipLaunchKernelGGL((k_ws_apply<Op, Src, Dst>), dim3(nb), dim3(BLOCK), 0, s->stream, src, dst,
+                       n, n_tiles, (const T*)tile_agg);
+}
+
+// ---- boundary pass: partition-start (bit 0) and peer-start (bit 1) flags ----
+struct WinKeys { // partition keys first, then the order keys
+    const void* col[2 * GPUE_WIN_MAX_KEYS];
+    const uint8_t* nul[2 * GPUE_WIN_MAX_KEYS];
+    uint8_t is64[2 * GPUE_WIN_MAX_KEYS];
+    int n_part, n_keys;
+};
+
+// The only kernel that reads order_idx unchecked: an index >= n is latched
+// into the session's error word and never dereferenced, and the host runs
+// nothing further on a latched error.
+__global__ __launch_bounds__(BLOCK) void
+k_win_flags(const WinKeys keys, const uint32_t* __restrict__ idx, uint64_t n,
+            uint8_t* __restrict__ flags, unsigned int* __restrict__ err) {
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        const uint64_t r = idx ? idx[i] : i;
+        const uint64_t rp = i == 0 ? r : (idx ? idx[i - 1] : i - 1);
+        uint32_t f = 3;
+        if (r >= n || rp >= n) {
+            atomicOr(err, AGG_ERR_WIN_IDX);
+        } else if (i != 0) {
+            bool pd = false, od = false;
+            for (int k = 0; k < keys.n_keys; k++) {
+                const bool na = keys.nul[k] && keys.nul[k][r] != 0;
+                const bool nb = keys.nul[k] && keys.nul[k][rp] != 0;
+                bool d = na != nb;
+                if (!na && !nb)
+                    d = keys.is64[k] ? ((const int64_t*)keys.col[k])[r] != ((const int64_t*)keys.col[k])[rp]
+                                     : ((const int32_t*)keys.col[k])[r] != ((const int32_t*)keys.col[k])[rp];
+                if (k < keys.n_part) pd = pd || d; else od = od || d;
+            }
+            f = pd ? 3u : (od ? 2u : 0u);
+        }
+        flags[i] = (uint8_t)f;
+    }
+}
+
+// ---- scan sources and sinks ----
+struct WsSrcBoundFwd {
+    const uint8_t* flags;
+    __device__ uint2 load(uint32_t p) const {
+        const uint32_t f = flags[p];
+        return make_uint2(f & 1u ? p : 0u, f & 2u ? p : 0u);
+    }
+};
+struct WsDstBoundFwd {
+    uint32_t *part_start, *peer_start;
+    __device__ void store(uint32_t p, uint2 v) const { part_start[p] = v.x; peer_start[p] = v.y; }
+};
+// mirror image: scan position p is row n-1-p, which ends a run iff row n-p starts one
+struct WsSrcBoundBwd {
+    const uint8_t* flags;
+    uint32_t n;
+    __device__ uint2 load(uint32_t p) const {
+        const uint32_t f = p == 0 ? 3u : flags[n - p];
+        return make_uint2(f & 1u ? p : 0u, f & 2u ? p : 0u);
+    }
+};
+struct WsDstBoundBwd {
+    uint32_t *part_end, *peer_end;
+    uint32_t n;
+    __device__ void store(uint32_t p, uint2 v) const {
+        part_end[n - 1 - p] = n - 1 - v.x;
+        peer_end[n - 1 - p] = n - 1 - v.y;
+    }
+};
+struct WinCol { // a function's input, read at a sorted position through order_idx
+    const void* col;
+    const uint8_t* nul;
+    const uint32_t* idx;
+    bool is64;
+    __device__ uint32_t row(uint32_t p) const { return idx ? idx[p] : p; }
+    __device__ bool is_null(uint32_t r) const { return nul && nul[r] != 0; }
+    __device__ int64_t value(uint32_t r) const {
+        return is64 ? ((const int64_t*)col)[r] : (int64_t)((const int32_t*)col)[r];
+    }
+};
+struct WsSrcVal { // SUM: NULL adds 0
+    WinCol c;
+    __device__ uint64_t load(uint32_t p) const {
+        const uint32_t r = c.row(p);
+        return c.is_null(r) ? 0ull : (uint64_t)c.value(r);
+    }
+};
+struct WsSrcNonNull {
+    WinCol c;
+    __device__ uint32_t load(uint32_t p) const { return c.is_null(c.row(p)) ? 0u : 1u; }
+};
+struct WsSrcPeer {
+    const uint8_t* flags;
+    __device__ uint32_t load(uint32_t p) const { return (flags[p] >> 1) & 1u; }
+};
+struct WsSrcSeg {
+    WinCol c;
+    const uint8_t* flags;
+    __device__ WsSeg load(uint32_t p) const {
+        const uint32_t r = c.row(p);
+        const bool has = !c.is_null(r);
+        return WsSeg{has ? c.value(r) : 0, (has ? 1u : 0u) | ((flags[p] & 1u) << 1)};
+    }
+};
+template <typename T>
+struct WsDstPlain {
+    T* out;
+    __device__ void store(uint32_t p, T v) const { out[p] = v; }
+};
+struct WsDstSeg {
+    int64_t* val;
+    uint32_t* has; // null when the input has no null column
+    __device__ void store(uint32_t p, WsSeg v) const {
+        val[p] = v.v;
+        if (has) has[p] = v.fl & 1u;
+    }
+};
+
+// ---- finish pass ----
+struct WinFn {
+    WinCol in;
+    const void* scan_a;     // SUM: u64 prefix sums; MIN / MAX: i64 running value
+    const uint32_t* scan_b; // non-NULL prefix counts / has-value flags / peer-group counts
+    int64_t* out;
+    uint8_t* out_nul;       // set iff the output is nullable
+    int64_t lo, hi, p0, p1;
+    int32_t fn, mode, has_default;
+};
+struct WinProg {
+    WinFn f[GPUE_WIN_MAX_FUNCS];
+    int n;
+};
+
+__global__ __launch_bounds__(BLOCK) void
+k_win_finish(const WinProg prog, const uint32_t* __restrict__ idx,
+             const uint32_t* __restrict__ part_start, const uint32_t* __restrict__ part_end,
+             const uint32_t* __restrict__ peer_start, const uint32_t* __restrict__ peer_end,
+             uint64_t n, bool sorted_out) {
+    const uint64_t stride = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+        const int64_t I = (int64_t)i, PS = part_start[i], QS = peer_start[i];
+        const int64_t PE = part_end ? part_end[i] : I, QE = peer_end ? peer_end[i] : I;
+        const uint64_t dst = sorted_out || !idx ? i : idx[i];
+        #pragma unroll 1
+        for (int k = 0; k < prog.n; k++) {
+            const WinFn& f = prog.f[k];
+            int64_t lo = PS, hi = PE;
+            if (f.mode == GPUE_WF_RANGE) {
+                if (f.hi == 0) hi = QE;
+            } else {
+                if (f.lo >= 0 && f.lo < I - PS) lo = I - f.lo;
+                if (f.hi >= 0 && f.hi < PE - I) hi = I + f.hi;
+            }
+            int64_t val = 0, pos = -1;
+            bool isnull = false;
+            switch (f.fn) {
+            case GPUE_WFN_ROW_NUMBER: val = I - PS + 1; break;
+            case GPUE_WFN_RANK: val = QS - PS + 1; break;
+            case GPUE_WFN_DENSE_RANK: val = (int64_t)(f.scan_b[I] - f.scan_b[PS]) + 1; break;
+            case GPUE_WFN_NTILE: {
+                const int64_t size = PE - PS + 1, q = size / f.p0, r = size % f.p0;
+                const int64_t rn0 = I - PS, thr = r * (q + 1);
+                val = rn0 < thr ? rn0 / (q + 1) + 1 : r + (rn0 - thr) / (q ? q : 1) + 1;
+                break;
+            }
+            case GPUE_WFN_COUNT_STAR: val = hi - lo + 1; break;
+            case GPUE_WFN_COUNT:
+                val = f.scan_b ? (int64_t)(uint32_t)(f.scan_b[hi] - (lo ? f.scan_b[lo - 1] : 0u))
+                               : hi - lo + 1;
+                break;
+            case GPUE_WFN_SUM: {
+                const uint64_t* P = (const uint64_t*)f.scan_a;
+                val = (int64_t)(P[hi] - (lo ? P[lo - 1] : 0ull)); // wrapping difference: exact
+                if (f.scan_b) isnull = f.scan_b[hi] == (lo ? f.scan_b[lo - 1] : 0u);
+                break;
+            }
+            case GPUE_WFN_MIN:
+            case GPUE_WFN_MAX: // lo == part_start: the running value at hi is the frame's
+                val = ((const int64_t*)f.scan_a)[hi];
+                if (f.scan_b) isnull = f.scan_b[hi] == 0;
+                break;
+            case GPUE_WFN_FIRST_VALUE: pos = lo; break;
+            case GPUE_WFN_LAST_VALUE: pos = hi; break;
+            case GPUE_WFN_LAG:
+                if (f.p0 <= I - PS) pos = I - f.p0;
+                else if (f.has_default) val = f.p1;
+                else isnull = true;
+                break;
+            default: // GPUE_WFN_LEAD
+                if (f.p0 <= PE - I) pos = I + f.p0;
+                else if (f.has_default) val = f.p1;
+                else isnull = true;
+                break;
+            }
+            if (pos >= 0) {
+                const uint32_t r = f.in.row((uint32_t)pos);
+                isnull = f.in.is_null(r);
+                if (!isnull) val = f.in.value(r);
+            }
+            f.out[dst] = isnull ? 0 : val;
+            if (f.out_nul) f.out_nul[dst] = isnull ? 1 : 0;
+        }
+    }
+}
+
+static inline bool win_fn_has_input(int fn) { return fn >= GPUE_WFN_COUNT; }
+static inline bool win_fn_framed(int fn) {
+    return fn >= GPUE_WFN_COUNT_STAR && fn <= GPUE_WFN_LAST_VALUE;
+}
+
+int gpue_window_eval(gpue_session* s, uint64_t n_rows, gpue_dbuf* order_idx,
+                     gpue_dbuf** part_cols, gpue_dbuf** part_nulls, const int32_t* part_type,
+                     const int32_t* part_nullable, int n_part,
+                     gpue_dbuf** order_cols, gpue_dbuf** order_nulls, const int32_t* order_type,
+                     const int32_t* order_nullable, int n_order,
+                     const int32_t* fn, gpue_dbuf** in_cols, gpue_dbuf** in_nulls,
+                     const int32_t* in_type, const int32_t* in_nullable,
+                     const int32_t* frame_mode, const int64_t* frame_lo, const int64_t* frame_hi,
+                     const int64_t* param0, const int64_t* param1, const int32_t* has_default,
+                     int n_funcs, gpue_dbuf** out_cols, gpue_dbuf** out_nulls, int flags) {
+    ARG_CHECK(s != nullptr);
+    ARG_CHECK(n_part >= 0 && n_part <= GPUE_WIN_MAX_KEYS);
+    ARG_CHECK(n_order >= 0 && n_order <= GPUE_WIN_MAX_KEYS);
+    ARG_CHECK(n_funcs >= 1 && n_funcs <= GPUE_WIN_MAX_FUNCS);
+    ARG_CHECK(flags == 0 || flags == GPUE_WIN_OUT_SORTED);
+    ARG_CHECK(n_rows < (1ull << 32));
+    ARG_CHECK(n_part == 0 || (part_cols && part_type && part_nullable));
+    ARG_CHECK(n_order == 0 || (order_cols && order_type && order_nullable));
+    ARG_CHECK(fn && out_cols);
+    const gpue_dbuf* rd[1 + 4 * GPUE_WIN_MAX_KEYS + 2 * GPUE_WIN_MAX_FUNCS];
+    const gpue_dbuf* wr[2 * GPUE_WIN_MAX_FUNCS];
+    int n_rd = 0, n_wr = 0;
+    if (order_idx) {
+        ARG_CHECK(order_idx->bytes >= n_rows * 4);
+        rd[n_rd++] = order_idx;
+    }
+    const uint32_t* idx = order_idx ? (const uint32_t*)order_idx->ptr : nullptr;
+    WinKeys keys;
+    memset(&keys, 0, sizeof(keys));
+    keys.n_part = n_part;
+    keys.n_keys = n_part + n_order;
+    for (int k = 0; k < n_part + n_order; k++) {
+        const bool part = k < n_part;
+        const int j = part ? k : k - n_part;
+        const int32_t type = (part ? part_type : order_type)[j];
+        const bool nullable = (part ? part_nullable : order_nullable)[j] != 0;
+        gpue_dbuf* col = (part ? part_cols : order_cols)[j];
+        gpue_dbuf** nls = part ? part_nulls : order_nulls;
+        gpue_dbuf* nl = nls ? nls[j] : nullptr;
+        ARG_CHECK(type == GPUE_PT_I32 || type == GPUE_PT_I64);
+        ARG_CHECK(col != nullptr); // missing key column
+        ARG_CHECK(col->bytes >= n_rows * (type == GPUE_PT_I64 ? 8u : 4u));
+        rd[n_rd++] = col;
+        if (nl) {
+            ARG_CHECK(nullable); // null buffer for a key declared NOT NULL
+            ARG_CHECK(nl->bytes >= n_rows);
+            rd[n_rd++] = nl;
+        }
+        keys.col[k] = col->ptr;
+        keys.nul[k] = nl ? (const uint8_t*)nl->ptr : nullptr;
+        keys.is64[k] = type == GPUE_PT_I64;
+    }
+    WinProg prog;
+    memset(&prog, 0, sizeof(prog));
+    prog.n = n_funcs;
+    bool need_bwd = false;
+    for (int a = 0; a < n_funcs; a++) {
+        WinFn& f = prog.f[a];
+        ARG_CHECK(fn[a] >= GPUE_WFN_ROW_NUMBER && fn[a] <= GPUE_WFN_LEAD);
+        f.fn = fn[a];
+        bool nullable_in = false;
+        if (win_fn_has_input(f.fn)) {
+            ARG_CHECK(in_cols && in_type && in_nullable);
+            ARG_CHECK(in_type[a] == GPUE_PT_I32 || in_type[a] == GPUE_PT_I64);
+            ARG_CHECK(in_cols[a] != nullptr); // missing input column
+            ARG_CHECK(in_cols[a]->bytes >= n_rows * (in_type[a] == GPUE_PT_I64 ? 8u : 4u));
+            rd[n_rd++] = in_cols[a];
+            nullable_in = in_nullable[a] != 0;
+            gpue_dbuf* nl = in_nulls ? in_nulls[a] : nullptr;
+            if (nl) {
+                ARG_CHECK(nullable_in); // null buffer for an input declared NOT NULL
+                ARG_CHECK(nl->bytes >= n_rows);
+                rd[n_rd++] = nl;
+            }
+            f.in = WinCol{in_cols[a]->ptr, nl ? (const uint8_t*)nl->ptr : nullptr, idx,
+                          in_type[a] == GPUE_PT_I64};
+        }
+        bool nullable_out = false;
+        if (win_fn_framed(f.fn)) {
+            ARG_CHECK(frame_mode && frame_lo && frame_hi);
+            ARG_CHECK(frame_mode[a] == GPUE_WF_ROWS || frame_mode[a] == GPUE_WF_RANGE);
+            ARG_CHECK(frame_lo[a] >= GPUE_WIN_UNBOUNDED && frame_hi[a] >= GPUE_WIN_UNBOUNDED);
+            if (frame_mode[a] == GPUE_WF_RANGE)
+                ARG_CHECK(frame_lo[a] == GPUE_WIN_UNBOUNDED &&
+                          (frame_hi[a] == 0 || frame_hi[a] == GPUE_WIN_UNBOUNDED));
+            if (f.fn == GPUE_WFN_MIN || f.fn == GPUE_WFN_MAX)
+                ARG_CHECK(frame_lo[a] == GPUE_WIN_UNBOUNDED); // no sliding minimum
+            f.mode = frame_mode[a];
+            f.lo = frame_lo[a];
+            f.hi = frame_hi[a];
+            nullable_out = f.fn >= GPUE_WFN_SUM && nullable_in;
+        } else if (f.fn == GPUE_WFN_NTILE) {
+            ARG_CHECK(param0 && param0[a] >= 1);
+            f.p0 = param0[a];
+        } else if (f.fn == GPUE_WFN_LAG || f.fn == GPUE_WFN_LEAD) {
+            ARG_CHECK(param0 && param0[a] >= 0);
+            ARG_CHECK(has_default && (!has_default[a] || param1));
+            f.p0 = param0[a];
+            f.has_default = has_default[a] != 0;
+            f.p1 = f.has_default ? param1[a] : 0;
+            nullable_out = !(f.has_default && !nullable_in);
+        }
+        need_bwd = need_bwd || !(f.fn <= GPUE_WFN_DENSE_RANK || f.fn == GPUE_WFN_LAG ||
+                                 f.fn == GPUE_WFN_FIRST_VALUE);
+        ARG_CHECK(out_cols[a] != nullptr);
+        ARG_CHECK(out_cols[a]->bytes >= n_rows * 8);
+        wr[n_wr++] = out_cols[a];
+        f.out = (int64_t*)out_cols[a]->ptr;
+        if (nullable_out) {
+            ARG_CHECK(out_nulls && out_nulls[a] != nullptr); // nullable output needs its null column
+            ARG_CHECK(out_nulls[a]->bytes >= n_rows);
+            wr[n_wr++] = out_nulls[a];
+            f.out_nul = (uint8_t*)out_nulls[a]->ptr;
+        }
+    }
+    auto overlap = [](const gpue_dbuf* x, const gpue_dbuf* y) {
+        const char *xa = (const char*)x->ptr, *ya = (const char*)y->ptr;
+        return xa < ya + y->bytes && ya < xa + x->bytes;
+    };
+    for (int i = 0; i < n_wr; i++) {
+        for (int j = i + 1; j < n_wr; j++) ARG_CHECK(!overlap(wr[i], wr[j]));
+        for (int j = 0; j < n_rd; j++) ARG_CHECK(!overlap(wr[i], rd[j]));
+    }
+    if (n_rows == 0) return GPUE_OK;
+    HIP_CHECK(hipSetDevice(s->device));
+
+    // scratch: one block, carved in 16-byte steps (sizes: gpue.h)
+    const uint64_t n = n_rows;
+    const uint32_t n_tiles = (uint32_t)((n + WS_TILE - 1) / WS_TILE);
+    uint64_t total = 0;
+    auto take = [&](uint64_t bytes) {
+        const uint64_t off = total;
+        total += (bytes + 15) & ~15ull;
+        return off;
+    };
+    const uint64_t o_flags = take(n), o_ps = take(4 * n), o_qs = take(4 * n);
+    const uint64_t o_pe = need_bwd ? take(4 * n) : 0, o_qe = need_bwd ? take(4 * n) : 0;
+    const uint64_t o_tiles = take((uint64_t)n_tiles * sizeof(WsSeg));
+    uint64_t o_a[GPUE_WIN_MAX_FUNCS] = {}, o_b[GPUE_WIN_MAX_FUNCS] = {};
+    bool has_a[GPUE_WIN_MAX_FUNCS] = {}, has_b[GPUE_WIN_MAX_FUNCS] = {};
+    for (int a = 0; a < n_funcs; a++) {
+        const WinFn& f = prog.f[a];
+        has_a[a] = f.fn == GPUE_WFN_SUM || f.fn == GPUE_WFN_MIN || f.fn == GPUE_WFN_MAX;
+        has_b[a] = f.fn == GPUE_WFN_DENSE_RANK ||
+                   ((has_a[a] || f.fn == GPUE_WFN_COUNT) && f.in.nul != nullptr);
+        if (has_a[a]) o_a[a] = take(8 * n);
+        if (has_b[a]) o_b[a] = take(4 * n);
+    }
+    PredTmp tmp;
+    HIP_CHECK(hipMalloc(&tmp.p, total));
+    char* base = (char*)tmp.p;
+    uint8_t* d_flags = (uint8_t*)(base + o_flags);
+    uint32_t *d_ps = (uint32_t*)(base + o_ps), *d_qs = (uint32_t*)(base + o_qs);
+    uint32_t* d_pe = need_bwd ? (uint32_t*)(base + o_pe) : nullptr;
+    uint32_t* d_qe = need_bwd ? (uint32_t*)(base + o_qe) : nullptr;
+    void* d_tiles = base + o_tiles;
+
+    hipLaunchKernelGGL(k_win_flags, dim3(grid_for(n)), dim3(BLOCK), 0, s->stream, keys, idx, n,
+                       d_flags, s->d_agg_err);
+    HIP_CHECK(hipGetLastError());
+    if (idx) { // a bad index stops the call here: every later pass reads through order_idx
+        HIP_CHECK(hipMemcpyAsync(s->pinned, s->d_agg_err, 4, hipMemcpyDeviceToHost, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        if (*(const volatile unsigned int*)s->pinned & AGG_ERR_WIN_IDX) {
+            HIP_CHECK(hipMemset(s->d_agg_err, 0, sizeof(unsigned int)));
+            snprintf(g_err, sizeof(g_err), "window_eval: order_idx holds an index >= n_rows");
+            return GPUE_ERR_ARG;
+        }
+    }
+    ws_scan<WsMax2>(s, WsSrcBoundFwd{d_flags}, WsDstBoundFwd{d_ps, d_qs}, n, n_tiles, d_tiles);
+    if (need_bwd)
+        ws_scan<WsMax2>(s, WsSrcBoundBwd{d_flags, (uint32_t)n},
+                        WsDstBoundBwd{d_pe, d_qe, (uint32_t)n}, n, n_tiles, d_tiles);
+    for (int a = 0; a < n_funcs; a++) {
+        WinFn& f = prog.f[a];
+        if (has_a[a]) f.scan_a = base + o_a[a];
+        if (has_b[a]) f.scan_b = (const uint32_t*)(base + o_b[a]);
+        uint32_t* d_b = has_b[a] ? (uint32_t*)(base + o_b[a]) : nullptr;
+        if (f.fn == GPUE_WFN_DENSE_RANK) {
+            ws_scan<WsAdd32>(s, WsSrcPeer{d_flags}, WsDstPlain<uint32_t>{d_b}, n, n_tiles, d_tiles);
+        } else if (f.fn == GPUE_WFN_SUM) {
+            ws_scan<WsAdd64>(s, WsSrcVal{f.in}, WsDstPlain<uint64_t>{(uint64_t*)(base + o_a[a])},
+                             n, n_tiles, d_tiles);
+        } else if (f.fn == GPUE_WFN_MIN) {
+            ws_scan<WsSegExt<false>>(s, WsSrcSeg{f.in, d_flags},
+                                     WsDstSeg{(int64_t*)(base + o_a[a]), d_b}, n, n_tiles, d_tiles);
+        } else if (f.fn == GPUE_WFN_MAX) {
+            ws_scan<WsSegExt<true>>(s, WsSrcSeg{f.in, d_flags},
+                                    WsDstSeg{(int64_t*)(base + o_a[a]), d_b}, n, n_tiles, d_tiles);
+        }
+        if (d_b && (f.fn == GPUE_WFN_SUM || f.fn == GPUE_WFN_COUNT))
+            ws_scan<WsAdd32>(s, WsSrcNonNull{f.in}, WsDstPlain<uint32_t>{d_b}, n, n_tiles, d_tiles);
+    }
+    hipLaunchKernelGGL(k_win_finish, dim3(grid_for(n)), dim3(BLOCK), 0, s->stream, prog, idx,
+                       (const uint32_t*)d_ps, (const uint32_t*)d_pe, (const uint32_t*)d_qs,
+                       (const uint32_t*)d_qe, n, flags == GPUE_WIN_OUT_SORTED);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s->stream)); // the scratch is freed on return
+    return GPUE_OK;
+}

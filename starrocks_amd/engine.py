@@ -232,6 +232,10 @@ def _declare(lib):
         "gpue_asof_probe_emit_i32": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_u64, c_i32,
                                              c_vp, c_vp, ctypes.POINTER(c_u64)]),
         "gpue_asof_table_destroy": (c_i32, [c_vp]),
+        "gpue_window_eval": (c_i32, [c_vp, c_u64, c_vp] +
+                             [ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_i32] * 2 +
+                             [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp)] + [c_vp] * 8 +
+                             [c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32]),
         "gpue_timer_start": (c_i32, [c_vp]),
         "gpue_timer_stop": (c_i32, [c_vp, ctypes.POINTER(ctypes.c_float)]),
     }
@@ -1345,6 +1349,87 @@ class Engine:
         idx = out.d2h(np.uint32, cnt)
         out.free()
         return idx
+
+    # --- window functions (gpue.h "window functions") ---
+    def window_eval(self, n_rows, order_idx, part_keys, order_keys, funcs, outs,
+                    sorted_out=False, flags=None):
+        """gpue_window_eval as it stands: order_idx a u32 permutation DBuf (or
+        None = rows already sorted), part_keys / order_keys = [(DBuf, nulls
+        DBuf or None, PT_I32 / PT_I64[, declared nullable])] (nullable iff a
+        null buffer is given unless stated), funcs = [window.WinFunc over
+        DBufs], outs = [(int64 DBuf, u8 nulls DBuf or None)]. No validation on
+        this side: what the C entry rejects comes back as GpueError."""
+        def key_args(keys):
+            nk = len(keys)
+            nullable = [k[3] if len(k) > 3 else k[1] is not None for k in keys]
+            return (self._vp_array([k[0] for k in keys], nk),
+                    self._vp_array([k[1] for k in keys], nk),
+                    np.array([k[2] for k in keys], np.int32),
+                    np.array([1 if x else 0 for x in nullable], np.int32), nk)
+        pc, pn, pt, pnl, npk = key_args(part_keys)
+        oc, on, ot, onl, nok = key_args(order_keys)
+        nf = len(funcs)
+        i32 = lambda xs: np.array([int(x) for x in xs], np.int32)
+        i64 = lambda xs: np.array([int(x) for x in xs], np.int64)
+        fn, it = i32(f.fn for f in funcs), i32(f.type for f in funcs)
+        inl, mode = i32(f.nullable for f in funcs), i32(f.mode for f in funcs)
+        lo, hi = i64(f.lo for f in funcs), i64(f.hi for f in funcs)
+        p0, p1 = i64(f.param0 for f in funcs), i64(f.param1 for f in funcs)
+        hd = i32(f.has_default for f in funcs)
+        if flags is None:
+            flags = 1 if sorted_out else 0
+        ptr = lambda a: a.ctypes.data_as(c_vp)
+        _ck(self._lib, self._lib.gpue_window_eval(
+            self._h, n_rows, order_idx._h if order_idx is not None else None,
+            pc, pn, ptr(pt), ptr(pnl), npk, oc, on, ptr(ot), ptr(onl), nok,
+            ptr(fn), self._vp_array([f.col for f in funcs], nf),
+            self._vp_array([f.nulls for f in funcs], nf), ptr(it), ptr(inl), ptr(mode),
+            ptr(lo), ptr(hi), ptr(p0), ptr(p1), ptr(hd), nf,
+            self._vp_array([o[0] for o in outs], nf),
+            self._vp_array([o[1] for o in outs], nf), flags))
+
+    def window(self, part_keys, order_keys, funcs, n_rows, sorted_out=False):
+        """One-shot fn(...) OVER (PARTITION BY ... ORDER BY ... frame):
+        part_keys = [(DBuf, nulls DBuf or None, PT_I32 / PT_I64)], order_keys
+        = [(DBuf, nulls DBuf or None, type, desc, nulls_first)], funcs =
+        [window.WinFunc over DBufs], the tuple style of project() /
+        group_agg(). Validates (ValueError), sorts with topn (partition keys
+        ascending NULLS FIRST, then the order keys under their flags, limit =
+        n_rows), allocates exact-size int64 outputs with u8 null buffers only
+        where the output is nullable, runs window_eval and frees the
+        permutation. Returns [(values, nulls or None), ...] lined up with the
+        input rows; with sorted_out they are in sorted order and the call
+        returns (results, permutation DBuf or None when n_rows == 0). The
+        inputs are left alone; everything allocated is freed on error."""
+        from starrocks_amd.window import WindowSpec
+        okeys = [(k[0], k[1], k[2]) for k in order_keys]
+        spec = WindowSpec.of(part_keys, okeys, funcs)
+        bufs, perm = [], None
+        try:
+            for nl in spec.out_nullable:
+                bufs.append(self.alloc(max(n_rows * 8, 1)))
+                bufs.append(self.alloc(max(n_rows, 1)) if nl else None)
+            outs = [(bufs[2 * a], bufs[2 * a + 1]) for a in range(spec.n_funcs)]
+            spec.check_eval(n_rows, None, [(k[0], k[1]) for k in part_keys],
+                            [(k[0], k[1]) for k in okeys],
+                            [(f.col, f.nulls) for f in funcs], outs, 1 if sorted_out else 0)
+            sort_keys = [(k[0], k[1], k[2], False, True) for k in part_keys] + \
+                        [(k[0], k[1], k[2], bool(k[3]), bool(k[4])) for k in order_keys]
+            if n_rows and sort_keys:
+                perm = self.alloc(n_rows * 4)
+                got = self.topn_into(sort_keys, n_rows, n_rows, 0, perm)
+                assert got == n_rows
+            self.window_eval(n_rows, perm, part_keys, okeys, funcs, outs, sorted_out)
+        except BaseException:
+            for b in bufs + [perm]:
+                if b is not None:
+                    b.free()
+            raise
+        if sorted_out:
+            return outs, perm
+        if perm is not None:
+            perm.free()
+        return outs
 
     # ---- stream event timing (bench) ----
     def timer_start(self):

@@ -778,6 +778,99 @@ class GroupAggSinkOperator(Operator):
         return g, hk, ha
 
 
+class WindowSinkOperator(Operator):
+    """fn(...) OVER (PARTITION BY ... ORDER BY ... frame) as a blocking sink
+    like TopNSinkOperator — the analytic operator's sink (exec/analytor.cpp),
+    which needs every row of a partition before it can answer.
+
+    Chunks are {"n": rows, "cols": [DBuf, ...]}; col_dtypes gives each chunk
+    column's numpy dtype (1-byte null masks, 4- or 8-byte values). part_map[i]
+    = (chunk column index, index of its u8 null mask or None, type 0 int32 /
+    1 int64), order_map[j] = the same plus (desc, nulls_first), and funcs =
+    [window.WinFunc whose col / nulls are chunk column indexes (or None)].
+
+    Per pushed chunk: every column is appended to a device column that
+    doubles as it fills, and the chunk's buffers are freed. set_finishing
+    runs Engine.window once over the whole input. result() returns (the
+    input columns as numpy arrays, [(values, nulls or None)] per function,
+    lined up with them).
+
+    Uses only engine.alloc / dbuf_d2d / window and DBuf.d2h / free, so it runs
+    against a numpy stand-in engine without a GPU."""
+
+    def __init__(self, engine, col_dtypes, part_map, order_map, funcs):
+        super().__init__()
+        from starrocks_amd.window import WindowSpec
+        self._e = engine
+        self._dtypes = [np.dtype(d) for d in col_dtypes]
+        self._part = [(int(c), None if nl is None else int(nl), t) for c, nl, t in part_map]
+        self._order = [(int(c), None if nl is None else int(nl), t, bool(d), bool(nf))
+                       for c, nl, t, d, nf in order_map]
+        self._funcs = list(funcs)
+        self.spec = WindowSpec([t for _, _, t in self._part],
+                               [nl is not None for _, nl, _ in self._part],
+                               [k[2] for k in self._order],
+                               [k[1] is not None for k in self._order], self._funcs)
+        self._cols = None
+        self._cap = 0
+        self.rows = 0
+        self._outs = None
+
+    def need_input(self):
+        return not self._finishing
+
+    def has_output(self):
+        return False
+
+    def _reserve(self, rows):
+        if self._cols is not None and rows <= self._cap:
+            return
+        cap = max(rows, 2 * self._cap, 1)
+        grown = [self._e.alloc(cap * dt.itemsize) for dt in self._dtypes]
+        if self._cols is not None:
+            for src, dst, dt in zip(self._cols, grown, self._dtypes):
+                if self.rows:
+                    self._e.dbuf_d2d(src, dst, self.rows * dt.itemsize, 0, 0)
+                src.free()
+        self._cols, self._cap = grown, cap
+
+    def push_chunk(self, chunk):
+        n, cols = chunk["n"], chunk["cols"]
+        try:
+            if n:
+                self._reserve(self.rows + n)
+                for src, dst, dt in zip(cols, self._cols, self._dtypes):
+                    self._e.dbuf_d2d(src, dst, n * dt.itemsize, 0, self.rows * dt.itemsize)
+                self.rows += n
+        finally:
+            for b in cols:
+                b.free()
+
+    def set_finishing(self):
+        if not self._finishing:
+            self._reserve(self.rows)
+            col = lambda i: None if i is None else self._cols[i]
+            self._outs = self._e.window(
+                [(col(c), col(nl), t) for c, nl, t in self._part],
+                [(col(c), col(nl), t, d, nf) for c, nl, t, d, nf in self._order],
+                [f.with_cols(col(f.col), col(f.nulls)) for f in self._funcs], self.rows)
+        super().set_finishing()
+
+    def result(self):
+        n = self.rows
+        pull = lambda b, dt: np.empty(0, dt) if n == 0 else b.d2h(dt, n)
+        try:
+            cols = [pull(b, dt) for b, dt in zip(self._cols, self._dtypes)]
+            outs = [(pull(v, np.int64), None if nl is None else pull(nl, np.uint8))
+                    for v, nl in self._outs]
+        finally:
+            for b in self._cols + [b for p in self._outs for b in p]:
+                if b is not None:
+                    b.free()
+            self._cols = self._outs = None
+        return cols, outs
+
+
 def q1_operator_pipeline(engine, seed, total_rows, year=1993,
                          chunk_rows=DEFAULT_CHUNK_ROWS, dim_chunk_rows=1000):
     """Config-2's plan as the reference would run it — dim source -> build
