@@ -761,6 +761,10 @@ int gpue_gather_u32(gpue_session* s, gpue_dbuf* in, gpue_dbuf* idx, uint64_t n,
                     gpue_dbuf* out);
 int gpue_gather_u64(gpue_session* s, gpue_dbuf* in, gpue_dbuf* idx, uint64_t n,
                     gpue_dbuf* out);
+/* 1-byte form of the same gather (Column::append_selective over a
+ * NullColumn's u8 data): carries null masks behind a sort permutation. */
+int gpue_gather_u8(gpue_session* s, gpue_dbuf* in, gpue_dbuf* idx, uint64_t n,
+                   gpue_dbuf* out);
 /* BIGINT-key partition (FNV over the 8 LE bytes of an int64 key column) */
 int gpue_partition_i64(gpue_session* s, gpue_dbuf* keys, uint64_t n, uint32_t num_channels,
                        uint64_t* start_points_out, gpue_dbuf* row_indexes_out);
@@ -811,6 +815,29 @@ int gpue_topn(gpue_session* s,
               uint64_t offset, uint64_t limit,
               gpue_dbuf* out_row_idx,    /* u32 row indices, in result order */
               uint64_t* out_count);
+/* Full sort: multi-key ORDER BY without LIMIT — the ChunksSorterFullSort
+ * result (reference exec/chunks_sorter_full_sort.cpp) under the same SortDesc
+ * as gpue_topn. out_row_idx receives the whole order, bit-identical to what
+ * gpue_topn writes for the same keys with offset = 0, limit = n_rows:
+ * lexicographic under each key's direction, NULL placement independent of the
+ * direction, the cell under a NULL never read into the order, rows equal on
+ * every key in ascending row index. Same key arguments and the same
+ * GPUE_ERR_ARG cases (before any launch or allocation) as gpue_topn, with
+ * out_row_idx at least n_rows*4 bytes; n_rows == 0 returns GPUE_OK with
+ * nothing written. Device side: a stable LSD radix sort (8-bit digits) over
+ * only the digits on which a key varies; up to GPUE_SORT_SMALL_MAX rows it
+ * runs gpue_topn's single-tile path instead. Workspace is allocated per call
+ * and freed on every path: at most 20 bytes per row (a second u32 row buffer
+ * and two 8-byte key-image buffers; 12 with only int32 keys) plus 1 MiB of
+ * block histograms. Payload columns are materialized by the caller with
+ * gpue_gather_u8/u32/u64 over out_row_idx. */
+#define GPUE_SORT_SMALL_MAX 2048
+int gpue_sort(gpue_session* s,
+              gpue_dbuf** key_cols, gpue_dbuf** key_nulls,
+              const int32_t* key_type,   /* GPUE_TOPN_I32 / _I64 / _U64 */
+              const int32_t* key_flags,  /* GPUE_TOPN_DESC | GPUE_TOPN_NULLS_FIRST */
+              int n_keys, uint64_t n_rows,
+              gpue_dbuf* out_row_idx);   /* u32[n_rows]: the whole order */
 
 /* ---- chunked-exchange overlap support (SURVEY.md §7 hard part (d)) ------
  * The session's HIP stream as an opaque pointer (wrap as a torch

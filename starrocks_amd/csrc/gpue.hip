@@ -2660,6 +2660,14 @@ __global__ void k_gather_u64(const uint64_t* __restrict__ in,
         out[i] = in[idx[i]];
 }
 
+__global__ void k_gather_u8(const uint8_t* __restrict__ in,
+                            const uint32_t* __restrict__ idx, uint64_t n,
+                            uint8_t* __restrict__ out) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = in[idx[i]];
+}
+
 // T is the column and literal type (int32_t / int64_t). d_filter and d_tc
 // live in `call` for the whole call, each compaction's buffers in a
 // DevScratch of its own, so every return frees what it allocated.
@@ -9381,6 +9389,18 @@ int gpue_gather_u32(gpue_session* s, gpue_dbuf* in, gpue_dbuf* idx, uint64_t n,
     return GPUE_OK;
 }
 
+// 1-byte form: null masks of payload columns behind a sort permutation
+int gpue_gather_u8(gpue_session* s, gpue_dbuf* in, gpue_dbuf* idx, uint64_t n,
+                   gpue_dbuf* out) {
+    ARG_CHECK(s && in && idx && out);
+    ARG_CHECK(idx->bytes >= n * 4 && out->bytes >= n);
+    hipLaunchKernelGGL(k_gather_u8, dim3(grid_for(n)), dim3(BLOCK), 0, s->stream,
+                       (const uint8_t*)in->ptr, (const uint32_t*)idx->ptr, n,
+                       (uint8_t*)out->ptr);
+    HIP_CHECK(hipGetLastError());
+    return GPUE_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Storage ingress: decode the reference's numeric page
 // body — bshuf_compress_lz4 framing (per block: 4-byte big-endian length +
@@ -10791,6 +10811,510 @@ int gpue_topn(gpue_session* s, gpue_dbuf** key_cols, gpue_dbuf** key_nulls,
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out_row_idx->ptr, d_surv + offset, count * 4,
                              hipMemcpyDeviceToDevice, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GPUE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Full sort — multi-key ORDER BY without LIMIT (reference
+// exec/chunks_sorter_full_sort.cpp under the same SortDesc): the whole order
+// of gpue_topn(offset 0, limit n_rows), bit for bit, by a stable LSD radix
+// sort over the (class, v) normalisation above instead of a bitonic network.
+//
+// Plan (one launch, one host read): per key, OR and AND of v over the non-NULL
+// rows and whether NULL / non-NULL rows exist. The host turns that into the
+// key's image: the bits of v from the lowest to the highest varying one, with
+// the 2-bit class on top when the key mixes NULL and non-NULL rows and the
+// image (32 bits for an int32 key, 64 otherwise) has room; if it has not,
+// the class gets a pass of its own that reads only the null mask. Only the
+// SORT_RBITS-bit digits of the image that contain a varying bit get a pass,
+// so a key on which nothing varies costs nothing.
+//
+// Passes run from the least significant key to the most significant, low
+// digit first, starting from the identity permutation; every pass is stable,
+// which makes ascending row index the last tie-break. A pass is
+//   hist    : per-block digit counts. On the first pass of a key it gathers
+//             col[perm[i]] / nulls[perm[i]], forms the image and stores it in
+//             position order, so the scattered read happens once per key;
+//   scan    : one block per digit turns its counts into per-block bases;
+//   scatter : streams (image, row), ranks each row inside its block and
+//             writes it at base + rank; the image travels with the row
+//             while the key has passes left.
+// No block waits for another. Inside a block each wave owns a contiguous
+// SORT_ITEMS*64 rows of the tile; lanes with the same digit find each other
+// by ballot on the digit bits, the first of them adds their number to the
+// wave's own LDS counter, and the waves' counters are combined after a
+// barrier — no LDS atomics, so nothing depends on arrival order.
+// ---------------------------------------------------------------------------
+static constexpr int SORT_RBITS = 8;
+static constexpr uint32_t SORT_NB = 1u << SORT_RBITS;
+static constexpr int SORT_ITEMS = 16;
+static constexpr uint32_t SORT_TILE = 4096;       // rows per block iteration
+static constexpr uint32_t SORT_MAX_BLOCKS = 1024; // 4 blocks/CU, as TOPN_MAX_BLOCKS
+static constexpr int SORT_NW = BLOCK / WAVE;
+static_assert(SORT_NB == (uint32_t)BLOCK, "one thread per digit in the combine steps");
+static_assert(SORT_TILE == (uint32_t)BLOCK * SORT_ITEMS, "tile = block x items");
+
+struct SortPlanKey { // one block's (then the host's) fold over one key
+    unsigned long long v_or, v_nand; // nand = OR of ~v, i.e. ~AND
+    unsigned int classes, pad;       // bit 0: a NULL row exists, bit 1: a non-NULL row
+};
+
+struct SortImage { // how a gather pass forms the image of one key
+    const void* col;
+    const uint8_t* nulls;
+    int32_t type, flags;
+    int32_t use_v;     // 0: class-only pass, the column is not read
+    int32_t lo;        // lowest varying bit of v
+    uint64_t vmask;    // (1 << span) - 1
+    int32_t cls_shift; // where the class goes, -1 = not in the image
+};
+
+__device__ static inline uint64_t sort_image(const SortImage& g, uint32_t row) {
+    uint32_t cls = 1u;
+    uint64_t v = 0;
+    if (g.use_v) topn_load(g.col, g.nulls, g.type, g.flags, row, cls, v);
+    else if (g.nulls && g.nulls[row]) cls = (g.flags & 2) ? 0u : 2u;
+    uint64_t w = (v >> g.lo) & g.vmask;
+    if (g.cls_shift >= 0) w |= (uint64_t)cls << g.cls_shift;
+    return w;
+}
+
+// Every block writes its own partial, plan[block][key], and the host folds
+// them, so the pass needs neither a memset nor same-address atomics.
+__global__ void __launch_bounds__(BLOCK)
+k_sort_plan(TopnKeys K, uint64_t n, SortPlanKey* __restrict__ plan) {
+    __shared__ SortPlanKey s_part[SORT_NW];
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (int k = 0; k < K.n_keys; k++) {
+        unsigned long long o = 0, na = 0;
+        unsigned int c = 0;
+        const uint8_t* nulls = K.nulls[k];
+        const int type = K.type[k], flags = K.flags[k];
+        // U rows per thread and step, indexes clamped instead of branched on so
+        // that the loads issue back to back (as topn_tile_load); the cell read
+        // under a NULL or past the end is discarded
+        constexpr int U = 8;
+        for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n;
+             i0 += stride * U) {
+            uint32_t nb[U];
+            uint64_t raw[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                uint64_t i = i0 + (uint64_t)u * stride;
+                uint64_t ic = i < n ? i : n - 1;
+                nb[u] = nulls ? nulls[ic] : 0u;
+                raw[u] = type == 0 ? (uint64_t)((const uint32_t*)K.col[k])[ic]
+                                   : ((const uint64_t*)K.col[k])[ic];
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                if (i0 + (uint64_t)u * stride >= n) continue;
+                if (nb[u]) {
+                    c |= 1u;
+                } else {
+                    uint64_t v = topn_norm_raw(raw[u], type, flags);
+                    o |= v;
+                    na |= ~v;
+                    c |= 2u;
+                }
+            }
+        }
+#pragma unroll
+        for (int d = WAVE / 2; d > 0; d >>= 1) {
+            o |= __shfl_xor(o, d);
+            na |= __shfl_xor(na, d);
+            c |= __shfl_xor(c, d);
+        }
+        if ((threadIdx.x & (WAVE - 1)) == 0) {
+            SortPlanKey& p = s_part[threadIdx.x / WAVE];
+            p.v_or = o;
+            p.v_nand = na;
+            p.classes = c;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            SortPlanKey r = s_part[0];
+            for (int w = 1; w < SORT_NW; w++) {
+                r.v_or |= s_part[w].v_or;
+                r.v_nand |= s_part[w].v_nand;
+                r.classes |= s_part[w].classes;
+            }
+            r.pad = 0;
+            plan[(uint64_t)blockIdx.x * TOPN_MAX_KEYS + k] = r;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void k_sort_iota(uint32_t* __restrict__ out, uint64_t n) {
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = (uint32_t)i;
+}
+
+// One item of every lane of a wave: lanes holding the same digit form a peer
+// set (ballot per digit bit). Returns the lane's rank among its peers plus
+// the wave's count of that digit so far; the first peer then adds the set's
+// size to the wave's counter. One wave's LDS accesses are served in order,
+// so the next item's read sees this write.
+__device__ static inline uint32_t sort_wave_rank(uint32_t digit, bool valid,
+                                                 uint32_t* __restrict__ cnt) {
+    unsigned long long peers = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < SORT_RBITS; b++) {
+        bool bit = (digit >> b) & 1u;
+        unsigned long long bal = __ballot(bit);
+        peers &= bit ? bal : ~bal;
+    }
+    uint32_t lane = threadIdx.x & (WAVE - 1);
+    uint32_t below = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
+    uint32_t pre = valid ? cnt[digit] : 0u;
+    __builtin_amdgcn_wave_barrier();
+    if (valid && below == 0) cnt[digit] = pre + (uint32_t)__popcll(peers);
+    __builtin_amdgcn_wave_barrier();
+    return pre + below;
+}
+
+// position of item j of this lane: waves own contiguous runs of the tile
+__device__ static inline uint64_t sort_item_pos(uint64_t tb, int j) {
+    uint32_t wave = threadIdx.x / WAVE, lane = threadIdx.x & (WAVE - 1);
+    return tb + (uint64_t)wave * (WAVE * SORT_ITEMS) + (uint64_t)j * WAVE + lane;
+}
+
+// Block b owns rows [b*chunk, (b+1)*chunk), chunk a multiple of SORT_TILE.
+// gather: img[i] = image of row perm[i] (perm NULL = identity) is computed and
+// stored; otherwise img holds it already.
+template <typename IMG>
+__global__ void __launch_bounds__(BLOCK)
+k_sort_hist(SortImage g, int gather, const uint32_t* __restrict__ perm, IMG* __restrict__ img,
+            uint64_t n, uint64_t chunk, int shift, uint32_t dmask,
+            uint32_t* __restrict__ blockhist) {
+    __shared__ uint32_t s_cnt[SORT_NW][SORT_NB];
+    for (int w = 0; w < SORT_NW; w++) s_cnt[w][threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t* cnt = s_cnt[threadIdx.x / WAVE];
+    uint64_t p0 = (uint64_t)blockIdx.x * chunk;
+    uint64_t p1 = p0 + chunk < n ? p0 + chunk : n;
+    for (uint64_t tb = p0; tb < p1; tb += SORT_TILE) {
+        IMG w[SORT_ITEMS];
+        if (gather) {
+            uint32_t row[SORT_ITEMS];
+#pragma unroll
+            for (int j = 0; j < SORT_ITEMS; j++) {
+                uint64_t pos = sort_item_pos(tb, j);
+                row[j] = pos < p1 ? (perm ? perm[pos] : (uint32_t)pos) : 0u;
+            }
+#pragma unroll
+            for (int j = 0; j < SORT_ITEMS; j++) {
+                uint64_t pos = sort_item_pos(tb, j);
+                w[j] = 0;
+                if (pos < p1) {
+                    w[j] = (IMG)sort_image(g, row[j]);
+                    img[pos] = w[j];
+                }
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < SORT_ITEMS; j++) {
+                uint64_t pos = sort_item_pos(tb, j);
+                w[j] = pos < p1 ? img[pos] : (IMG)0;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            (void)sort_wave_rank((uint32_t)(w[j] >> shift) & dmask, sort_item_pos(tb, j) < p1,
+                                 cnt);
+    }
+    __syncthreads();
+    uint32_t total = 0;
+    for (int w = 0; w < SORT_NW; w++) total += s_cnt[w][threadIdx.x];
+    // digit-major, so that the scan of one digit over the blocks is contiguous
+    blockhist[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x] = total;
+}
+
+// block d: blockhist[d][b] becomes the count of digit d in blocks before b,
+// digit_total[d] its count in all of them. (One block walking the nb
+// histograms in sequence, the first form of this kernel, made a call 12-14 %
+// slower at 10^7 rows: DESIGN.md §4i.)
+__global__ void __launch_bounds__(BLOCK)
+k_sort_scan(uint32_t* __restrict__ blockhist, uint32_t nb, uint32_t* __restrict__ digit_total) {
+    __shared__ unsigned long long s_scan[BLOCK];
+    constexpr int PER = SORT_MAX_BLOCKS / BLOCK;
+    static_assert(SORT_MAX_BLOCKS % BLOCK == 0, "each thread scans PER blocks");
+    uint32_t* col = blockhist + (uint64_t)blockIdx.x * nb;
+    uint32_t c[PER], sum = 0;
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+        uint32_t b = threadIdx.x * PER + j;
+        c[j] = b < nb ? col[b] : 0u;
+        sum += c[j];
+    }
+    unsigned long long incl = topn_block_scan((unsigned long long)sum, s_scan);
+    uint32_t run = (uint32_t)(incl - sum);
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+        uint32_t b = threadIdx.x * PER + j;
+        if (b < nb) col[b] = run;
+        run += c[j];
+    }
+    if (threadIdx.x == BLOCK - 1) digit_total[blockIdx.x] = (uint32_t)incl;
+}
+
+// stable scatter of (image, row) by one digit; perm_in NULL = identity,
+// img_out NULL = the key has no pass left and its image is dropped
+template <typename IMG>
+__global__ void __launch_bounds__(BLOCK)
+k_sort_scatter(const uint32_t* __restrict__ perm_in, const IMG* __restrict__ img_in,
+               uint32_t* __restrict__ perm_out, IMG* __restrict__ img_out, uint64_t n,
+               uint64_t chunk, int shift, uint32_t dmask,
+               const uint32_t* __restrict__ blockbase, const uint32_t* __restrict__ digit_total) {
+    __shared__ uint32_t s_cnt[SORT_NW][SORT_NB];
+    __shared__ unsigned long long s_scan[BLOCK];
+    const uint32_t wave = threadIdx.x / WAVE;
+    // thread d keeps where the block's next row of digit d goes: rows of
+    // smaller digits, then rows of digit d in earlier blocks
+    uint32_t tot = digit_total[threadIdx.x];
+    uint32_t base = (uint32_t)(topn_block_scan((unsigned long long)tot, s_scan) - tot) +
+                    blockbase[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x];
+    uint64_t p0 = (uint64_t)blockIdx.x * chunk;
+    uint64_t p1 = p0 + chunk < n ? p0 + chunk : n;
+    for (uint64_t tb = p0; tb < p1; tb += SORT_TILE) {
+        for (int w = 0; w < SORT_NW; w++) s_cnt[w][threadIdx.x] = 0;
+        __syncthreads();
+        IMG w[SORT_ITEMS];
+        uint32_t row[SORT_ITEMS], off[SORT_ITEMS];
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++) {
+            uint64_t pos = sort_item_pos(tb, j);
+            w[j] = pos < p1 ? img_in[pos] : (IMG)0;
+            row[j] = pos < p1 ? (perm_in ? perm_in[pos] : (uint32_t)pos) : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            off[j] = sort_wave_rank((uint32_t)(w[j] >> shift) & dmask,
+                                    sort_item_pos(tb, j) < p1, s_cnt[wave]);
+        __syncthreads();
+        // counts per wave -> where each wave's rows of digit d start
+        uint32_t at = base;
+        for (int v = 0; v < SORT_NW; v++) {
+            uint32_t c = s_cnt[v][threadIdx.x];
+            s_cnt[v][threadIdx.x] = at;
+            at += c;
+        }
+        base = at;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++) {
+            if (sort_item_pos(tb, j) < p1) {
+                uint64_t dst = (uint64_t)s_cnt[wave][(uint32_t)(w[j] >> shift) & dmask] + off[j];
+                if (dst < n) { // holds whenever hist and scatter saw the same images
+                    perm_out[dst] = row[j];
+                    if (img_out) img_out[dst] = w[j];
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+namespace {
+struct SortWork { // frees the call's scratch on every return path
+    void* p[2] = {nullptr, nullptr};
+    ~SortWork() {
+        for (void* q : p)
+            if (q) (void)hipFree(q);
+    }
+};
+
+struct SortPass {
+    int key;
+    bool gather;  // first pass of its key (or class-only): hist forms the image
+    bool carry;   // the key has a later streamed pass: scatter keeps the image
+    int shift;
+    uint32_t dmask;
+    SortImage img;
+};
+
+template <typename IMG>
+void sort_launch_pass(gpue_session* s, const SortPass& p, const uint32_t* perm_in,
+                      uint32_t* perm_out, void* img_in, void* img_out, uint64_t n, uint32_t nb,
+                      uint64_t chunk, uint32_t* blockhist, uint32_t* digit_total) {
+    hipLaunchKernelGGL(k_sort_hist<IMG>, dim3(nb), dim3(BLOCK), 0, s->stream, p.img,
+                       p.gather ? 1 : 0, perm_in, (IMG*)img_in, n, chunk, p.shift, p.dmask,
+                       blockhist);
+    hipLaunchKernelGGL(k_sort_scan, dim3(SORT_NB), dim3(BLOCK), 0, s->stream, blockhist, nb,
+                       digit_total);
+    hipLaunchKernelGGL(k_sort_scatter<IMG>, dim3(nb), dim3(BLOCK), 0, s->stream, perm_in,
+                       (const IMG*)img_in, perm_out, (IMG*)(p.carry ? img_out : nullptr), n,
+                       chunk, p.shift, p.dmask, (const uint32_t*)blockhist,
+                       (const uint32_t*)digit_total);
+}
+} // namespace
+
+int gpue_sort(gpue_session* s, gpue_dbuf** key_cols, gpue_dbuf** key_nulls,
+              const int32_t* key_type, const int32_t* key_flags, int n_keys, uint64_t n_rows,
+              gpue_dbuf* out_row_idx) {
+    ARG_CHECK(s && key_cols && key_type && key_flags);
+    ARG_CHECK(n_keys >= 1 && n_keys <= TOPN_MAX_KEYS);
+    ARG_CHECK(n_rows < (1ull << 32));
+    TopnKeys K;
+    memset(&K, 0, sizeof(K));
+    K.n_keys = n_keys;
+    for (int k = 0; k < n_keys; k++) {
+        ARG_CHECK(key_type[k] >= 0 && key_type[k] <= 2);
+        ARG_CHECK(key_cols[k] != nullptr);
+        ARG_CHECK(key_cols[k]->bytes >= n_rows * (key_type[k] == 0 ? 4u : 8u));
+        gpue_dbuf* nm = key_nulls ? key_nulls[k] : nullptr;
+        ARG_CHECK(!nm || nm->bytes >= n_rows);
+        K.col[k] = key_cols[k]->ptr;
+        K.nulls[k] = nm ? (const uint8_t*)nm->ptr : nullptr;
+        K.type[k] = key_type[k];
+        K.flags[k] = key_flags[k] & 3;
+    }
+    const uint64_t n = n_rows;
+    ARG_CHECK(n == 0 || (out_row_idx && out_row_idx->bytes >= n * 4));
+    if (n == 0) return GPUE_OK;
+
+    // one LDS tile: the single-tile bitonic path needs no plan read and two
+    // launches (GPUE_SORT_SMALL_MAX overrides the switch for experiments)
+    static_assert(GPUE_SORT_SMALL_MAX <= TOPN_SORT_TILE, "the small path is one LDS tile");
+    uint64_t small_max = GPUE_SORT_SMALL_MAX;
+    if (const char* e = getenv("GPUE_SORT_SMALL_MAX")) small_max = strtoull(e, nullptr, 10);
+    if (n <= small_max && n <= TOPN_SORT_TILE) {
+        uint64_t cnt = 0;
+        return gpue_topn(s, key_cols, key_nulls, key_type, key_flags, n_keys, n, 0, n,
+                         out_row_idx, &cnt);
+    }
+    const bool regather = getenv("GPUE_SORT_REGATHER") != nullptr; // the rejected variant
+
+    SortWork w;
+    constexpr uint32_t PLAN_BLOCKS = 256; // one streaming block per CU
+    constexpr uint64_t PLAN_SLOT = sizeof(SortPlanKey) * TOPN_MAX_KEYS;
+    static_assert(PLAN_BLOCKS * PLAN_SLOT <= gpue_session::PINNED_BYTES, "plan read is one bounce");
+    const uint32_t plan_nb = grid_capped(n, PLAN_BLOCKS);
+    HIP_CHECK(hipMalloc(&w.p[0], PLAN_SLOT * plan_nb));
+    hipLaunchKernelGGL(k_sort_plan, dim3(plan_nb), dim3(BLOCK), 0, s->stream, K, n,
+                       (SortPlanKey*)w.p[0]);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(s->pinned, w.p[0], PLAN_SLOT * plan_nb, hipMemcpyDeviceToHost,
+                             s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    SortPlanKey plan[TOPN_MAX_KEYS];
+    memset(plan, 0, sizeof(plan));
+    for (uint32_t b = 0; b < plan_nb; b++) {
+        const SortPlanKey* part = (const SortPlanKey*)s->pinned + (uint64_t)b * TOPN_MAX_KEYS;
+        for (int k = 0; k < n_keys; k++) {
+            plan[k].v_or |= part[k].v_or;
+            plan[k].v_nand |= part[k].v_nand;
+            plan[k].classes |= part[k].classes;
+        }
+    }
+
+    // pass list, least significant key first, low digit first
+    SortPass pass[TOPN_MAX_KEYS * 9];
+    int n_pass = 0;
+    bool any64 = false, any_carry = false;
+    for (int k = n_keys - 1; k >= 0; k--) {
+        const int W = K.type[k] == 0 ? 32 : 64;
+        const bool mixed = plan[k].classes == 3u;
+        uint64_t vary = (plan[k].classes & 2u) ? (plan[k].v_or & plan[k].v_nand) : 0ull;
+        if (W == 32) vary &= 0xFFFFFFFFull;
+        const int lo = vary ? __builtin_ctzll(vary) : 0;
+        const int span = vary ? 64 - __builtin_clzll(vary) - lo : 0;
+        const bool fold = mixed && span + 2 <= W;
+        SortImage g;
+        memset(&g, 0, sizeof(g));
+        g.col = K.col[k];
+        g.nulls = K.nulls[k];
+        g.type = K.type[k];
+        g.flags = K.flags[k];
+        g.use_v = 1;
+        g.lo = lo;
+        g.vmask = span >= 64 ? ~0ull : (1ull << span) - 1ull;
+        g.cls_shift = fold ? span : -1;
+        uint64_t bits = vary >> lo; // varying bits of the image
+        if (fold) bits |= 3ull << span;
+        const int width = span + (fold ? 2 : 0);
+        const int first = n_pass;
+        for (int sh = 0; sh < width; sh += SORT_RBITS) {
+            int nbits = width - sh < SORT_RBITS ? width - sh : SORT_RBITS;
+            uint32_t dmask = (1u << nbits) - 1u;
+            if (((bits >> sh) & dmask) == 0) continue;
+            SortPass& p = pass[n_pass++];
+            p.key = k;
+            p.gather = regather || n_pass - 1 == first;
+            p.carry = false;
+            p.shift = sh;
+            p.dmask = dmask;
+            p.img = g;
+        }
+        if (!regather)
+            for (int i = first; i + 1 < n_pass; i++) pass[i].carry = any_carry = true;
+        if (mixed && !fold) { // no room for the class: a pass over the null mask alone
+            SortPass& p = pass[n_pass++];
+            p.key = k;
+            p.gather = true;
+            p.carry = false;
+            p.shift = 0;
+            p.dmask = 3u;
+            p.img = g;
+            p.img.use_v = 0;
+            p.img.lo = 0;
+            p.img.vmask = 0;
+            p.img.cls_shift = 0;
+        }
+        if (n_pass > first && W == 64) any64 = true;
+    }
+
+    uint32_t* d_out = (uint32_t*)out_row_idx->ptr;
+    if (n_pass == 0) { // nothing varies on any key: the order is the row order
+        hipLaunchKernelGGL(k_sort_iota, dim3(grid_stream(n)), dim3(BLOCK), 0, s->stream, d_out,
+                           n);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        return GPUE_OK;
+    }
+
+    const uint64_t tiles = (n + SORT_TILE - 1) / SORT_TILE;
+    const uint64_t per = (tiles + SORT_MAX_BLOCKS - 1) / SORT_MAX_BLOCKS; // tiles per block
+    const uint32_t nb = (uint32_t)((tiles + per - 1) / per);
+    const uint64_t chunk = per * SORT_TILE;
+
+    // workspace: block histograms + digit totals, the second row buffer (two
+    // passes or more), one image buffer and a second where a key is carried
+    const uint64_t img_b = ((any64 ? 8u : 4u) * n + 255) & ~255ull;
+    const uint64_t row_b = (4 * n + 255) & ~255ull;
+    const uint64_t hist_b = (uint64_t)nb * SORT_NB * 4 + SORT_NB * 4;
+    HIP_CHECK(hipMalloc(&w.p[1], hist_b + (n_pass > 1 ? row_b : 0) +
+                                     img_b * (any_carry ? 2 : 1)));
+    char* at = (char*)w.p[1];
+    uint32_t* blockhist = (uint32_t*)at;
+    uint32_t* digit_total = blockhist + (uint64_t)nb * SORT_NB;
+    at += hist_b;
+    uint32_t* rows[2] = {d_out, nullptr};
+    if (n_pass > 1) {
+        rows[1] = (uint32_t*)at;
+        at += row_b;
+    }
+    void* img[2] = {at, any_carry ? at + img_b : nullptr};
+
+    int ib = 0; // image buffer that holds (or receives) the current key's image
+    for (int i = 0; i < n_pass; i++) {
+        const SortPass& p = pass[i];
+        // the last pass lands in out_row_idx; pass 0 reads the identity
+        const uint32_t* perm_in = i == 0 ? nullptr : rows[(n_pass - i) & 1];
+        uint32_t* perm_out = rows[(n_pass - 1 - i) & 1];
+        if (p.gather) ib = 0;
+        if (K.type[p.key] == 0)
+            sort_launch_pass<uint32_t>(s, p, perm_in, perm_out, img[ib], img[ib ^ 1], n, nb,
+                                       chunk, blockhist, digit_total);
+        else
+            sort_launch_pass<uint64_t>(s, p, perm_in, perm_out, img[ib], img[ib ^ 1], n, nb,
+                                       chunk, blockhist, digit_total);
+        HIP_CHECK(hipGetLastError());
+        if (p.carry) ib ^= 1;
+    }
     HIP_CHECK(hipStreamSynchronize(s->stream));
     return GPUE_OK;
 }

@@ -149,6 +149,7 @@ def _declare(lib):
         "gpue_partition_varchar": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_u32, c_vp, c_vp]),
         "gpue_gather_u32": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_vp]),
         "gpue_gather_u64": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_vp]),
+        "gpue_gather_u8": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_vp]),
         "gpue_partition_i64": (c_i32, [c_vp, c_vp, c_u64, c_u32, c_vp, c_vp]),
         "gpue_partition_2xi32": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_u32, c_vp, c_vp]),
         "gpue_gen_lineitem_q3": (c_i32, [c_vp, c_u64, c_u64, c_u64, c_u64] + [c_vp] * 4),
@@ -214,6 +215,8 @@ def _declare(lib):
         "gpue_topk_i64": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_i32, c_vp, c_vp]),
         "gpue_topn": (c_i32, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp,
                               c_i32, c_u64, c_u64, c_u64, c_vp, ctypes.POINTER(c_u64)]),
+        "gpue_sort": (c_i32, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp,
+                              c_i32, c_u64, c_vp]),
         "gpue_page_decode_rle_i32": (c_i32, [c_vp, c_vp, c_u64, c_vp]),
         "gpue_page_decode_plain_i32": (c_i32, [c_vp, c_vp, c_u64, c_vp]),
         "gpue_page_decode_rle_bool": (c_i32, [c_vp, c_vp, c_u64, c_vp]),
@@ -1112,6 +1115,9 @@ class Engine:
     def gather_u64(self, inp: DBuf, idx: DBuf, n, out: DBuf):
         _ck(self._lib, self._lib.gpue_gather_u64(self._h, inp._h, idx._h, n, out._h))
 
+    def gather_u8(self, inp: DBuf, idx: DBuf, n, out: DBuf):
+        _ck(self._lib, self._lib.gpue_gather_u8(self._h, inp._h, idx._h, n, out._h))
+
     def partition_i64(self, keys: DBuf, n, num_channels, row_indexes: DBuf) -> np.ndarray:
         sp = np.zeros(num_channels + 1, dtype=np.uint64)
         _ck(self._lib, self._lib.gpue_partition_i64(self._h, keys._h, n, num_channels,
@@ -1350,6 +1356,44 @@ class Engine:
         out.free()
         return idx
 
+    # --- full sort (chunks_sorter_full_sort.cpp under the same SortDesc) ---
+    SORT_TILE = 4096          # rows per block iteration of a radix pass (gpue.hip)
+    SORT_MAX_BLOCKS = 1024    # grid cap: past SORT_MAX_BLOCKS tiles a block loops
+    SORT_SMALL_MAX = 2048     # up to here gpue_sort runs topn's single-tile path
+
+    def sort_into(self, keys, n_rows, out: DBuf):
+        """gpue_sort into a caller-owned u32[n_rows] buffer (out may be None
+        when n_rows is 0): the whole order, bit-identical to topn_into(keys,
+        n_rows, n_rows, 0, out). keys as topn_into."""
+        nk = len(keys)
+        cols = (c_vp * max(nk, 1))(*[k[0]._h for k in keys])
+        nulls = (c_vp * max(nk, 1))(*[k[1]._h if k[1] is not None else None for k in keys])
+        types = np.array([k[2] for k in keys], np.int32)
+        flags = np.array([(1 if k[3] else 0) | (2 if k[4] else 0) for k in keys], np.int32)
+        _ck(self._lib, self._lib.gpue_sort(
+            self._h, cols, nulls, types.ctypes.data_as(c_vp), flags.ctypes.data_as(c_vp),
+            nk, n_rows, out._h if out is not None else None))
+
+    def sort(self, keys, n_rows) -> DBuf:
+        """Multi-key ORDER BY without LIMIT: a device buffer of the n_rows u32
+        row indices in sorted order (rows equal on every key in ascending row
+        index). Materialize payload columns with gather_u8/u32/u64."""
+        out = self.alloc(max(n_rows, 1) * 4)
+        try:
+            self.sort_into(keys, n_rows, out)
+        except BaseException:
+            out.free()
+            raise
+        return out
+
+    def sort_indices(self, keys, n_rows) -> np.ndarray:
+        """sort() with the row indices copied to the host."""
+        out = self.sort(keys, n_rows)
+        try:
+            return out.d2h(np.uint32, n_rows) if n_rows else np.empty(0, np.uint32)
+        finally:
+            out.free()
+
     # --- window functions (gpue.h "window functions") ---
     def window_eval(self, n_rows, order_idx, part_keys, order_keys, funcs, outs,
                     sorted_out=False, flags=None):
@@ -1393,7 +1437,7 @@ class Engine:
         part_keys = [(DBuf, nulls DBuf or None, PT_I32 / PT_I64)], order_keys
         = [(DBuf, nulls DBuf or None, type, desc, nulls_first)], funcs =
         [window.WinFunc over DBufs], the tuple style of project() /
-        group_agg(). Validates (ValueError), sorts with topn (partition keys
+        group_agg(). Validates (ValueError), sorts with sort_into (partition keys
         ascending NULLS FIRST, then the order keys under their flags, limit =
         n_rows), allocates exact-size int64 outputs with u8 null buffers only
         where the output is nullable, runs window_eval and frees the
@@ -1417,8 +1461,7 @@ class Engine:
                         [(k[0], k[1], k[2], bool(k[3]), bool(k[4])) for k in order_keys]
             if n_rows and sort_keys:
                 perm = self.alloc(n_rows * 4)
-                got = self.topn_into(sort_keys, n_rows, n_rows, 0, perm)
-                assert got == n_rows
+                self.sort_into(sort_keys, n_rows, perm)
             self.window_eval(n_rows, perm, part_keys, okeys, funcs, outs, sorted_out)
         except BaseException:
             for b in bufs + [perm]:

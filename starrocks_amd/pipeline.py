@@ -778,6 +778,47 @@ class GroupAggSinkOperator(Operator):
         return g, hk, ha
 
 
+class _GrowingColumns:
+    """The blocking sinks' input store: one device column per chunk column,
+    doubling as it fills. append() copies a chunk in and frees its buffers."""
+
+    def __init__(self, engine, dtypes):
+        self._e = engine
+        self._dtypes = dtypes
+        self.cols = None
+        self._cap = 0
+        self.rows = 0
+
+    def reserve(self, rows):
+        if self.cols is not None and rows <= self._cap:
+            return
+        cap = max(rows, 2 * self._cap, 1)
+        grown = [self._e.alloc(cap * dt.itemsize) for dt in self._dtypes]
+        if self.cols is not None:
+            for src, dst, dt in zip(self.cols, grown, self._dtypes):
+                if self.rows:
+                    self._e.dbuf_d2d(src, dst, self.rows * dt.itemsize, 0, 0)
+                src.free()
+        self.cols, self._cap = grown, cap
+
+    def append(self, chunk):
+        n, cols = chunk["n"], chunk["cols"]
+        try:
+            if n:
+                self.reserve(self.rows + n)
+                for src, dst, dt in zip(cols, self.cols, self._dtypes):
+                    self._e.dbuf_d2d(src, dst, n * dt.itemsize, 0, self.rows * dt.itemsize)
+                self.rows += n
+        finally:
+            for b in cols:
+                b.free()
+
+    def release(self):
+        """Hand the columns to the caller to free; the row count stays."""
+        cols, self.cols = self.cols or [], None
+        return cols
+
+
 class WindowSinkOperator(Operator):
     """fn(...) OVER (PARTITION BY ... ORDER BY ... frame) as a blocking sink
     like TopNSinkOperator — the analytic operator's sink (exec/analytor.cpp),
@@ -811,10 +852,12 @@ class WindowSinkOperator(Operator):
                                [nl is not None for _, nl, _ in self._part],
                                [k[2] for k in self._order],
                                [k[1] is not None for k in self._order], self._funcs)
-        self._cols = None
-        self._cap = 0
-        self.rows = 0
+        self._acc = _GrowingColumns(engine, self._dtypes)
         self._outs = None
+
+    @property
+    def rows(self):
+        return self._acc.rows
 
     def need_input(self):
         return not self._finishing
@@ -822,34 +865,13 @@ class WindowSinkOperator(Operator):
     def has_output(self):
         return False
 
-    def _reserve(self, rows):
-        if self._cols is not None and rows <= self._cap:
-            return
-        cap = max(rows, 2 * self._cap, 1)
-        grown = [self._e.alloc(cap * dt.itemsize) for dt in self._dtypes]
-        if self._cols is not None:
-            for src, dst, dt in zip(self._cols, grown, self._dtypes):
-                if self.rows:
-                    self._e.dbuf_d2d(src, dst, self.rows * dt.itemsize, 0, 0)
-                src.free()
-        self._cols, self._cap = grown, cap
-
     def push_chunk(self, chunk):
-        n, cols = chunk["n"], chunk["cols"]
-        try:
-            if n:
-                self._reserve(self.rows + n)
-                for src, dst, dt in zip(cols, self._cols, self._dtypes):
-                    self._e.dbuf_d2d(src, dst, n * dt.itemsize, 0, self.rows * dt.itemsize)
-                self.rows += n
-        finally:
-            for b in cols:
-                b.free()
+        self._acc.append(chunk)
 
     def set_finishing(self):
         if not self._finishing:
-            self._reserve(self.rows)
-            col = lambda i: None if i is None else self._cols[i]
+            self._acc.reserve(self.rows)
+            col = lambda i: None if i is None else self._acc.cols[i]
             self._outs = self._e.window(
                 [(col(c), col(nl), t) for c, nl, t in self._part],
                 [(col(c), col(nl), t, d, nf) for c, nl, t, d, nf in self._order],
@@ -860,15 +882,99 @@ class WindowSinkOperator(Operator):
         n = self.rows
         pull = lambda b, dt: np.empty(0, dt) if n == 0 else b.d2h(dt, n)
         try:
-            cols = [pull(b, dt) for b, dt in zip(self._cols, self._dtypes)]
+            cols = [pull(b, dt) for b, dt in zip(self._acc.cols, self._dtypes)]
             outs = [(pull(v, np.int64), None if nl is None else pull(nl, np.uint8))
                     for v, nl in self._outs]
         finally:
-            for b in self._cols + [b for p in self._outs for b in p]:
+            for b in self._acc.release() + [b for p in self._outs for b in p]:
                 if b is not None:
                     b.free()
-            self._cols = self._outs = None
+            self._outs = None
         return cols, outs
+
+
+class SortSinkOperator(Operator):
+    """ORDER BY without LIMIT as a blocking sink — the full-sort chunks sorter
+    (exec/chunks_sorter_full_sort.cpp), which holds every row until the input
+    ends.
+
+    Chunks are {"n": rows, "cols": [DBuf, ...]} and col_dtypes gives each
+    chunk column's numpy dtype (1-byte null masks, 4- or 8-byte values), as
+    for WindowSinkOperator. key_map[i] = (chunk column index, index of its u8
+    null mask or None, type 0 int32 / 1 int64 / 2 uint64, desc, nulls_first),
+    most significant first.
+
+    Per pushed chunk every column is appended to a growing device column and
+    the chunk's buffers are freed. set_finishing sorts once (Engine.sort) and
+    gathers every column, null masks included, through the permutation with
+    gather_u8 / _u32 / _u64 by item size. result() returns the columns in
+    sorted order as numpy arrays. Rows equal on every key keep arrival order:
+    the sort's tie-break is the row index, which here is the arrival ordinal.
+
+    Uses only engine.alloc / dbuf_d2d / sort / gather_* and DBuf.d2h / free, so
+    it runs against a numpy stand-in engine without a GPU."""
+
+    def __init__(self, engine, col_dtypes, key_map):
+        super().__init__()
+        self._e = engine
+        self._dtypes = [np.dtype(d) for d in col_dtypes]
+        for dt in self._dtypes:
+            if dt.itemsize not in (1, 4, 8):
+                raise ValueError(f"column item size {dt.itemsize} not in 1, 4, 8")
+        self._keys = [(int(c), None if nl is None else int(nl), t, bool(d), bool(nf))
+                      for c, nl, t, d, nf in key_map]
+        self._acc = _GrowingColumns(engine, self._dtypes)
+        self._sorted = None
+
+    @property
+    def rows(self):
+        return self._acc.rows
+
+    def need_input(self):
+        return not self._finishing
+
+    def has_output(self):
+        return False
+
+    def push_chunk(self, chunk):
+        self._acc.append(chunk)
+
+    def set_finishing(self):
+        if not self._finishing:
+            n = self.rows
+            self._acc.reserve(n)
+            cols = self._acc.cols
+            col = lambda i: None if i is None else cols[i]
+            gather = {1: self._e.gather_u8, 4: self._e.gather_u32, 8: self._e.gather_u64}
+            perm, out = None, []
+            try:
+                perm = self._e.sort([(col(c), col(nl), t, d, nf)
+                                     for c, nl, t, d, nf in self._keys], n)
+                for src, dt in zip(cols, self._dtypes):
+                    out.append(self._e.alloc(max(n, 1) * dt.itemsize))
+                    if n:
+                        gather[dt.itemsize](src, perm, n, out[-1])
+            except BaseException:
+                for b in out:
+                    b.free()
+                raise
+            finally:
+                if perm is not None:
+                    perm.free()
+                for b in self._acc.release():
+                    b.free()
+            self._sorted = out
+        super().set_finishing()
+
+    def result(self):
+        n = self.rows
+        try:
+            return [np.empty(0, dt) if n == 0 else b.d2h(dt, n)
+                    for b, dt in zip(self._sorted, self._dtypes)]
+        finally:
+            for b in self._sorted:
+                b.free()
+            self._sorted = None
 
 
 def q1_operator_pipeline(engine, seed, total_rows, year=1993,
