@@ -164,6 +164,16 @@ struct gpue_join_table {
                                     // words [0,8192) = i & MASK18,
                                     // [8192,16384) = (i*2654435761)>>14 —
                                     // the bloom-k=2 experiment (mode 6)
+    // alias-resolved fold A (q21 mode 10): which of the up to three keys
+    // i, i + 2^19, i + 2^20 behind a set bit i of prefilter2w's fold A pass.
+    // Kept when first16c exists, the pass set spans at most 3 * 2^19 keys and
+    // fold A has at most 65,535 set bits (all three null otherwise)
+    uint16_t* alias_pref = nullptr;  // u16[4096]: set bits of fold A before
+                                     // 128-bit block b
+    uint32_t* alias_codes = nullptr; // 2 bits per set bit, in bit order, 65,536
+                                     // entries zero-padded: 0..2 = the one
+                                     // passing alias (idx >> 19), 3 = several
+    uint32_t alias_nset = 0;         // set bits of fold A
     uint2* dense_groups = nullptr; // DENSE_RANGE_DIRECT: per-32-key group
                                    // {start_index, bitset} (rank/select slot map,
                                    // join_hash_map_method.h:378, .hpp:781-904)
@@ -1769,6 +1779,94 @@ static int join_table_rank_payloads(gpue_session* s, gpue_join_table* t, uint64_
     return GPUE_OK;
 }
 
+// Per-128-bit-block popcount of fold A (2^19 bits = 4096 blocks) and its
+// exclusive scan, one workgroup of 1024 threads, four blocks per thread.
+// pref is u16: exact whenever the total is at most 65,535, the only case in
+// which the caller keeps it.
+__global__ __launch_bounds__(1024) void
+k_alias_scan(const uint32_t* __restrict__ folda, uint16_t* __restrict__ pref,
+             uint32_t* __restrict__ nset) {
+    __shared__ uint32_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint4* __restrict__ f4 = (const uint4*)folda;
+    uint32_t c[4], sum = 0;
+    #pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint4 w = f4[4 * t + k];
+        c[k] = __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w);
+        sum += c[k];
+    }
+    part[t] = sum;
+    __syncthreads();
+    for (uint32_t off = 1; off < 1024; off <<= 1) {
+        uint32_t v = t >= off ? part[t - off] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - sum;
+    #pragma unroll
+    for (int k = 0; k < 4; k++) {
+        pref[4 * t + k] = (uint16_t)run;
+        run += c[k];
+    }
+    if (t == 1023) *nset = part[t];
+}
+
+// One 2-bit code per set bit j of fold A, at that bit's rank: the alias
+// a = i >> 19 of the one passing key i = j + a * 2^19, or 3 when several pass
+// (codes zeroed by the caller; set_interval <= 3 * 2^19).
+__global__ void k_alias_fill(const uint32_t* __restrict__ bitset, uint64_t set_interval,
+                             const uint32_t* __restrict__ folda,
+                             const uint16_t* __restrict__ pref, uint32_t* __restrict__ codes) {
+    uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < (1u << 19); j += stride) {
+        uint32_t w = folda[j >> 5];
+        if (!((w >> (j & 31)) & 1u)) continue;
+        uint32_t pos = pref[j >> 7];
+        for (uint32_t k = (j >> 7) * 4; k < (j >> 5); k++) pos += __popc(folda[k]);
+        pos += __popc(w & ((1u << (j & 31)) - 1));
+        uint32_t cnt = 0, code = 0;
+        for (uint32_t a = 0; a < 3; a++) {
+            uint64_t i = (uint64_t)j + ((uint64_t)a << 19);
+            if (i < set_interval && ((bitset[i >> 5] >> (i & 31)) & 1u)) {
+                cnt++;
+                code = a;
+            }
+        }
+        if (cnt > 1) code = 3;
+        if (code) atomicOr(&codes[pos >> 4], code << (2 * (pos & 15)));
+    }
+}
+
+// Alias-resolved fold A of a ranked payload table (alias_pref / alias_codes /
+// alias_nset), left null where the pass set spans more than three aliases or
+// fold A has more than 65,535 set bits. Synchronises the stream once.
+static int join_table_alias_fold(gpue_session* s, gpue_join_table* t, uint64_t set_interval) {
+    if (!t->first16c || !t->prefilter2w || set_interval > 3ull << 19) return GPUE_OK;
+    DevScratch tmp;
+    uint32_t* d_nset = nullptr;
+    HIP_CHECK(tmp.alloc(&d_nset, sizeof(uint32_t)));
+    HIP_CHECK(hipMalloc(&t->alias_pref, 4096 * sizeof(uint16_t)));
+    hipLaunchKernelGGL(k_alias_scan, dim3(1), dim3(1024), 0, s->stream, t->prefilter2w,
+                       t->alias_pref, d_nset);
+    uint32_t nset = 0;
+    HIP_CHECK(hipMemcpyAsync(&nset, d_nset, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    if (nset > 65535) {
+        (void)hipFree(t->alias_pref);
+        t->alias_pref = nullptr;
+        return GPUE_OK;
+    }
+    HIP_CHECK(hipMalloc(&t->alias_codes, 65536 / 4));
+    HIP_CHECK(hipMemsetAsync(t->alias_codes, 0, 65536 / 4, s->stream));
+    hipLaunchKernelGGL(k_alias_fill, dim3(grid_for(1u << 19)), dim3(BLOCK), 0, s->stream,
+                       t->bitset, set_interval, t->prefilter2w, t->alias_pref, t->alias_codes);
+    HIP_CHECK(hipGetLastError());
+    t->alias_nset = nset;
+    return GPUE_OK;
+}
+
 __global__ void k_build_range_direct(const int32_t* __restrict__ keys, uint64_t row_count,
                                      int64_t min_key, uint32_t* __restrict__ first,
                                      uint32_t* __restrict__ next) {
@@ -1869,6 +1967,8 @@ int gpue_join_build_payload_i32(gpue_session* s, gpue_dbuf* keys, gpue_dbuf* pay
     if (t->first16) {
         rc = join_table_rank_payloads(s, t, interval);
         if (rc != GPUE_OK) return rc;
+        rc = join_table_alias_fold(s, t, set_interval);
+        if (rc != GPUE_OK) return rc;
     }
     *out = own.release();
     return GPUE_OK;
@@ -1911,6 +2011,8 @@ void gpue_join_table_destroy(gpue_join_table* t) {
     if (t->prefilter) (void)hipFree(t->prefilter);
     if (t->prefilter2) (void)hipFree(t->prefilter2);
     if (t->prefilter2w) (void)hipFree(t->prefilter2w);
+    if (t->alias_pref) (void)hipFree(t->alias_pref);
+    if (t->alias_codes) (void)hipFree(t->alias_codes);
     if (t->dense_groups) (void)hipFree(t->dense_groups);
     if (t->build_keys) (void)hipFree(t->build_keys);
     if (t->key_bytes) (void)hipFree(t->key_bytes);
@@ -5630,6 +5732,204 @@ k_q21_star_agg_pfq5(const int32_t* __restrict__ pk, const int32_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------
+// Alias-resolved q21 (GPUE_Q21_PF=10): pfq5<19, ., .> with fold B's probe and
+// the per-maybe first16c gather replaced by the table's alias codes in LDS.
+//  push:   one probe of fold A (2^19 bits, index idx & M19); maybes go to Q1
+//          as {pk, row};
+//  drain1: no global access. pos = the rank of the key's bit among fold A's
+//          set bits (alias_pref of its 128-bit block + popcounts inside the
+//          block), code = alias_codes[pos]; the key survives iff code == 3
+//          (several aliases of the bit pass) or code == idx >> 19 (it is the
+//          one alias that passes). Survivors go to Q2 as {row, pk};
+//  drain2: pfq5's supplier test; forwards {row, pk} to Q3;
+//  drain3: od, rv and first16c[pk - 1] together, then the date gather. The
+//          rank is 0 for a non-passing key on a several-alias bit: that skip
+//          is the exact rejection, required for the result.
+// The burst loop, guards and final flush are pfq5's. A register-double-
+// buffered next burst, loaded before the current one is pushed, measured flat
+// here as it did on pfq5 and is not kept.
+// Fills, as proved above pfq4 / pfq5. Q1CAP >= 320: the wave-uniform guard
+// before each quad drains full batches while n1 + 256 > Q1CAP (then n1 > 64,
+// a full batch is there), so the quad's <= 256 pushes keep Q1 <= Q1CAP.
+// Q1CAP == 128 drains after each key's push (Q1 <= 127). Every drain1 is
+// followed at once by the tail's threshold drains, so Q2 <= 127, Q3 <= 127 and
+// Q2 + Q3 <= 190 = QS. LDS: 65,536 fold A + 8,192 pref + 16,384 codes + 3,584
+// groups + 24,320 Q2/Q3 + 128 * Q1CAP Q1 (158,976 B at Q1CAP = 320), static,
+// 1 block/CU. Every fill comes from a ballot, all loop conditions are
+// wave-uniform, the kernel is blockDim-agnostic (64..1024), row ids are 32-bit.
+// ---------------------------------------------------------------------------
+template <int Q1CAP, int K>
+__global__ __launch_bounds__(BLOCK_Q21) void
+k_q21_star_agg_pfq6(const int32_t* __restrict__ pk, const int32_t* __restrict__ sk,
+                    const int32_t* __restrict__ od, const int32_t* __restrict__ rv,
+                    uint64_t n, const uint32_t* __restrict__ folda,
+                    const uint16_t* __restrict__ apref, const uint32_t* __restrict__ acodes,
+                    int64_t psmin, uint64_t psint, const uint16_t* __restrict__ pfirstc,
+                    const uint16_t* __restrict__ pay_vals, uint32_t n_pay,
+                    const uint32_t* __restrict__ sbits, int64_t ssmin, uint64_t ssint,
+                    const uint16_t* __restrict__ dfirst, int64_t dmin,
+                    unsigned long long* __restrict__ group_sums) {
+    static_assert(Q1CAP == 128 || Q1CAP >= 320, "see the fill bounds above");
+    static_assert(K >= 1 && (K == 1 || Q1CAP >= 320), "a burst needs the per-quad guard");
+    constexpr bool PERKEY = Q1CAP == 128;
+    constexpr int QS = 126 + 64;
+    constexpr uint32_t M19 = (1u << 19) - 1;
+    __shared__ __attribute__((aligned(16))) uint32_t pfa[1 << 14];
+    __shared__ uint16_t pref[1 << 12];
+    __shared__ uint32_t codes[1 << 12];
+    __shared__ unsigned long long g[7 * NBC];
+    __shared__ int2 q1[BLOCK_Q21 / WAVE][Q1CAP];    // {pk, row32}
+    __shared__ uint32_t qrow[BLOCK_Q21 / WAVE][QS]; // Q2 up from 0, Q3 down from QS-1
+    __shared__ uint32_t qpk[BLOCK_Q21 / WAVE][QS];
+    for (uint32_t w = threadIdx.x; w < (1u << 14); w += blockDim.x) pfa[w] = folda[w];
+    for (uint32_t w = threadIdx.x; w < (1u << 12); w += blockDim.x) {
+        pref[w] = apref[w];
+        codes[w] = acodes[w];
+    }
+    for (uint32_t j = threadIdx.x; j < 7 * NBC; j += blockDim.x) g[j] = 0;
+    __syncthreads();
+    const int wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t n1 = 0, n2 = 0, n3 = 0; // wave-uniform fills (ballot counts)
+    const uint64_t n4 = n / 4;
+    const int4* __restrict__ pk4 = (const int4*)pk;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    // cnt = 64 for a full batch, the fill at the final flush
+    auto drain3 = [&](uint32_t cnt) {
+        bool act = lane < cnt;
+        uint32_t slot = QS - 1 - (n3 - cnt + lane);
+        uint32_t r = act ? qrow[wid][slot] : 0u;
+        uint32_t key = act ? qpk[wid][slot] : 0u;
+        n3 -= cnt;
+        if (act) {
+            int32_t o = od[r];
+            int32_t v = rv[r];
+            uint32_t rank1 = pfirstc[key - 1]; // exact category filter (0 = fail)
+            uint32_t y = dfirst[o - dmin];
+            if (rank1) atomicAdd(&g[(y - 1) * NBC + (rank1 - 1)], (unsigned long long)(int64_t)v);
+        }
+    };
+    auto drain2 = [&](uint32_t cnt) {
+        bool act = lane < cnt;
+        uint32_t r = act ? qrow[wid][n2 - cnt + lane] : 0u;
+        uint32_t key = act ? qpk[wid][n2 - cnt + lane] : 0u;
+        n2 -= cnt;
+        bool pass = false;
+        if (act) {
+            uint32_t sidx = (uint32_t)(sk[r] - ssmin);
+            pass = sidx < ssint && ((sbits[sidx >> 5] >> (sidx & 31)) & 1u);
+        }
+        uint64_t m = __ballot(pass);
+        if (m) {
+            if (pass) {
+                uint32_t slot = QS - 1 - (n3 + __popcll(m & below));
+                qrow[wid][slot] = r;
+                qpk[wid][slot] = key;
+            }
+            n3 += __popcll(m);
+            if (n3 >= 64) drain3(64);
+        }
+    };
+    auto drain1 = [&](uint32_t cnt) {
+        bool act = lane < cnt;
+        int2 e = act ? q1[wid][n1 - cnt + lane] : make_int2((int32_t)psmin, 0);
+        n1 -= cnt;
+        // every Q1 entry is in range with its fold A bit set, so pos is below
+        // alias_nset <= 65,535; idle lanes read bit 0's block
+        uint32_t idx = (uint32_t)(e.x - psmin);
+        uint32_t j = idx & M19, a = idx >> 19;
+        uint4 blk = ((const uint4*)pfa)[j >> 7];
+        uint32_t wsel = (j >> 5) & 3, lowm = (1u << (j & 31)) - 1;
+        uint32_t pos = pref[j >> 7];
+        pos += __popc(blk.x & (wsel == 0 ? lowm : ~0u));
+        pos += wsel >= 1 ? __popc(blk.y & (wsel == 1 ? lowm : ~0u)) : 0u;
+        pos += wsel >= 2 ? __popc(blk.z & (wsel == 2 ? lowm : ~0u)) : 0u;
+        pos += wsel >= 3 ? __popc(blk.w & lowm) : 0u;
+        uint32_t code = (codes[(pos >> 4) & 4095] >> (2 * (pos & 15))) & 3u;
+        bool pass = act & ((code == 3) | (code == a));
+        uint64_t m = __ballot(pass);
+        if (m) {
+            if (pass) {
+                uint32_t slot = n2 + __popcll(m & below);
+                qrow[wid][slot] = (uint32_t)e.y;
+                qpk[wid][slot] = (uint32_t)e.x;
+            }
+            n2 += __popcll(m);
+            if (n2 >= 64) drain2(64);
+        }
+    };
+    auto push = [&](int32_t key, uint32_t row, bool inb) {
+        uint32_t idx = (uint32_t)(key - psmin);
+        bool in = inb & (idx < psint);
+        uint32_t ia = (in ? idx : 0u) & M19;
+        bool maybe = in & (pfa[ia >> 5] >> (ia & 31)) & 1u;
+        uint64_t m = __ballot(maybe);
+        if (m) {
+            if (maybe) q1[wid][n1 + __popcll(m & below)] = make_int2(key, (int32_t)row);
+            n1 += __popcll(m);
+            if constexpr (PERKEY)
+                if (n1 >= 64) drain1(64);
+        }
+    };
+    auto quad = [&](int4 p, uint64_t qi, bool inb) {
+        if constexpr (!PERKEY)
+            while (n1 + 256 > Q1CAP) drain1(64); // overflow guard, once per quad
+        #pragma unroll
+        for (int j = 0; j < 4; j++) push((&p.x)[j], (uint32_t)(qi * 4 + j), inb);
+    };
+    auto ld4nt = [&](const int4* p, uint64_t i) {
+        const uint64_t* q = (const uint64_t*)(p + i);
+        uint64_t lo = __builtin_nontemporal_load(q);
+        uint64_t hi = __builtin_nontemporal_load(q + 1);
+        int4 v;
+        v.x = (int32_t)lo; v.y = (int32_t)(lo >> 32);
+        v.z = (int32_t)hi; v.w = (int32_t)(hi >> 32);
+        return v;
+    };
+    uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (uint64_t)wid * WAVE;
+    uint64_t i = base + lane;
+    // bursts of K quads, all of them full-wave
+    for (; base + (K - 1) * stride + WAVE <= n4; base += K * stride, i += K * stride) {
+        int4 p[K];
+        #pragma unroll
+        for (int k = 0; k < K; k++) p[k] = ld4nt(pk4, i + k * stride);
+        #pragma unroll
+        for (int k = 0; k < K; k++) quad(p[k], i + k * stride, true);
+        while (n1 >= 64) drain1(64);
+    }
+    for (; base < n4; base += stride, i += stride) {
+        bool inb = i < n4;
+        int4 p4 = inb ? pk4[i] : make_int4(0, 0, 0, 0);
+        quad(p4, i, inb);
+        while (n1 >= 64) drain1(64);
+    }
+    // final flush, in stage order: each partial drain leaves the next stage
+    // below its threshold again before that stage's own partial drain
+    if (n1 > 0) drain1(n1);
+    if (n2 > 0) drain2(n2);
+    if (n3 > 0) drain3(n3);
+    // scalar row tail (n % 4): exact path
+    uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t r = n4 * 4 + tid; r < n; r += stride) {
+        uint32_t idx = (uint32_t)(pk[r] - psmin);
+        if (idx >= psint) continue;
+        uint32_t rank1 = pfirstc[pk[r] - 1];
+        if (!rank1) continue;
+        uint32_t sidx = (uint32_t)(sk[r] - ssmin);
+        if (sidx >= ssint || !((sbits[sidx >> 5] >> (sidx & 31)) & 1u)) continue;
+        uint32_t year1 = dfirst[od[r] - dmin];
+        atomicAdd(&g[(year1 - 1) * NBC + (rank1 - 1)], (unsigned long long)(int64_t)rv[r]);
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < 7 * n_pay; j += blockDim.x) {
+        uint32_t y = j / n_pay, r = j - y * n_pay;
+        unsigned long long v = g[y * NBC + r];
+        if (v != 0) atomicAdd(&group_sums[y * 1000 + pay_vals[r] - 1], v);
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Two-stream pipelined q21 (GPUE_Q21_PIPE=1): the fused kernel's streaming
 // leg (1.57 ms) and its part-probe gather leg (2.32 ms) measured fully
 // ADDITIVE (profiles/q21_decomp.log) — so split them into an operator pair
@@ -5808,6 +6108,13 @@ static bool q21_pf() {
 // sessions of 5 interleaved runs (profiles/r04_q21_compact_ab.log)
 static constexpr int Q21_PF9_DEFAULT_VAR = 4;
 
+// The GPUE_Q21_PF10_VAR that runs when GPUE_Q21_PF is unset and the part table
+// carries alias codes (0 would leave mode 9 the default there). Var 2's
+// slowest run was faster than the parent default's fastest in two sessions of
+// 5 interleaved runs: 0.9293 < 0.9999 and 0.9136 < 1.0103
+// (profiles/r05_q21_alias_ab.log)
+static constexpr int Q21_PF10_DEFAULT_VAR = 2;
+
 extern "C" int gpue_q21_star_agg_async(gpue_session* s, gpue_join_table* parts,
                                        gpue_join_table* supps, gpue_join_table* dates,
                                        gpue_dbuf* pk, gpue_dbuf* sk, gpue_dbuf* od,
@@ -5824,10 +6131,15 @@ int gpue_q21_star_agg_async(gpue_session* s, gpue_join_table* parts, gpue_join_t
         const char* e = getenv("GPUE_Q21_PF");
         // mode 9 (compact groups, k_q21_star_agg_pfq5) needs the part table's
         // dense payload rank and the 1000-brand output layout; it is the
-        // default where it can run, mode 8 var 11 stays the default elsewhere
+        // default where it can run and mode 10 cannot, mode 8 var 11 stays
+        // the default elsewhere
         const bool compact_ok = parts->first16c && parts->prefilter2 && parts->prefilter2w &&
                                 parts->pay_max <= 1000 && n <= UINT32_MAX;
-        int mode = e ? atoi(e) : (compact_ok && Q21_PF9_DEFAULT_VAR > 0) ? 9 : 8;
+        // mode 10 (alias-resolved fold, k_q21_star_agg_pfq6) needs mode 9's
+        // table and the alias codes on top
+        const bool alias_ok = compact_ok && parts->alias_pref && parts->alias_codes;
+        int mode = e ? atoi(e) : (alias_ok && Q21_PF10_DEFAULT_VAR > 0) ? 10 :
+                   (compact_ok && Q21_PF9_DEFAULT_VAR > 0) ? 9 : 8;
                                     // 8 = staged cascade + prefetched pk stream
                                     // over mode 7's deferred loads: 1.015-
                                     // 1.040 (median 1.027) vs mode 7's 1.105-
@@ -5863,7 +6175,33 @@ int gpue_q21_star_agg_async(gpue_session* s, gpue_join_table* parts, gpue_join_t
         };
         // modes 7 and 8 queue row ids as 32 bits
         ARG_CHECK((mode != 7 && mode != 8) || n <= UINT32_MAX);
-        if (mode == 9) { // compact groups + wider fold / burst-drained pk stream
+        if (mode == 10) { // alias codes in LDS: one probe per key, LDS-only drain1
+            ARG_CHECK(alias_ok);
+            // GPUE_Q21_PF10_VAR, read per call: the (Q1CAP, K) of
+            // k_q21_star_agg_pfq6. 1 = (128, 1) the per-key drain control;
+            // 2 = (320, 4) the burst. Medians of 5 interleaved runs, ms/step,
+            // two sessions, against the parent commit's binary (mode 9 var 4)
+            // at 1.0108 / 1.0201: 1 = 0.9802 / 0.9869, 2 = 0.9144 / 0.9128
+            int var = (int)env_cap("GPUE_Q21_PF10_VAR",
+                                   Q21_PF10_DEFAULT_VAR > 0 ? Q21_PF10_DEFAULT_VAR : 2);
+            ARG_CHECK(var >= 1 && var <= 2);
+            auto launch10 = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(env_cap("GPUE_GRID_PF", def_grid)),
+                                   dim3(tpb), 0, s->stream, (const int32_t*)pk->ptr,
+                                   (const int32_t*)sk->ptr, (const int32_t*)od->ptr,
+                                   (const int32_t*)rv->ptr, n, parts->prefilter2w,
+                                   parts->alias_pref, parts->alias_codes, parts->set_min,
+                                   (uint64_t)(parts->set_max - parts->set_min + 1),
+                                   parts->first16c, parts->pay_vals, parts->n_pay,
+                                   supps->bitset, supps->set_min,
+                                   (uint64_t)(supps->set_max - supps->set_min + 1),
+                                   dates->first16, dates->min_key,
+                                   (unsigned long long*)group_sums->ptr);
+            };
+            if (var == 1) launch10(k_q21_star_agg_pfq6<128, 1>);
+            else launch10(k_q21_star_agg_pfq6<320, 4>);
+        }
+        else if (mode == 9) { // compact groups + wider fold / burst-drained pk stream
             ARG_CHECK(compact_ok);
             // GPUE_Q21_PF9_VAR, read per call: the (FA, Q1CAP, K) of
             // k_q21_star_agg_pfq5. 1 = (18, 128, 1) the control: compact
@@ -6846,6 +7184,88 @@ k_ub_q21_pf_legs(const int32_t* __restrict__ pk, const int32_t* __restrict__ sk,
     if (g[threadIdx.x & (NG_Q21 - 1)] > ~0ull - 1) sink[0] = 0; // keep g live
 }
 
+// Push-path legs of k_q21_star_agg_pfq5<19, 320, 4> / pfq6<320, 4> at their
+// geometry (K = 4 NT bursts of the pk stream, 16 x 320 Q1, 1 block/CU):
+// LEG 0 = the pk stream alone, 1 = + pfq5's push (fold A and fold B probes,
+// ballot, Q1 write), 2 = + pfq6's push (fold A only). Full batches are
+// dropped where the kernels drain them, so Q1's fills move as they do there
+// and nothing behind Q1 runs. folds = fold A's 2^14 words, then fold B's 2^13.
+template <int LEG>
+__global__ __launch_bounds__(BLOCK_Q21) void
+k_ub_q21_push(const int32_t* __restrict__ pk, uint64_t n, const uint32_t* __restrict__ folds,
+              int64_t psmin, uint64_t psint, unsigned long long* __restrict__ sink) {
+    constexpr int Q1CAP = 320, K = 4;
+    constexpr uint32_t M19 = (1u << 19) - 1;
+    __shared__ uint32_t pfa[1 << 14];
+    __shared__ uint32_t pfb[1 << 13];
+    __shared__ int2 q1[BLOCK_Q21 / WAVE][Q1CAP];
+    if (LEG >= 1)
+        for (uint32_t w = threadIdx.x; w < (1u << 14); w += blockDim.x) pfa[w] = folds[w];
+    if (LEG == 1)
+        for (uint32_t w = threadIdx.x; w < (1u << 13); w += blockDim.x)
+            pfb[w] = folds[(1u << 14) + w];
+    for (uint32_t w = threadIdx.x; w < BLOCK_Q21 / WAVE * Q1CAP; w += blockDim.x)
+        (&q1[0][0])[w] = make_int2(0, 0);
+    __syncthreads();
+    const int wid = threadIdx.x / WAVE;
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t n1 = 0;
+    unsigned long long acc = 0;
+    const uint64_t n4 = n / 4;
+    const int4* __restrict__ pk4 = (const int4*)pk;
+    uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    auto push = [&](int32_t key, uint32_t row) {
+        uint32_t idx = (uint32_t)(key - psmin);
+        bool in = idx < psint;
+        uint32_t ia = (in ? idx : 0u) & M19;
+        bool maybe = in & (pfa[ia >> 5] >> (ia & 31)) & 1u;
+        if (LEG == 1) {
+            uint32_t ib = ((in ? idx : 0u) * 2654435761u) >> 14;
+            maybe &= (pfb[ib >> 5] >> (ib & 31)) & 1u;
+        }
+        uint64_t m = __ballot(maybe);
+        if (m) {
+            if (maybe) q1[wid][n1 + __popcll(m & below)] = make_int2(key, (int32_t)row);
+            n1 += __popcll(m);
+        }
+    };
+    auto ld4nt = [&](const int4* p, uint64_t i) {
+        const uint64_t* q = (const uint64_t*)(p + i);
+        uint64_t lo = __builtin_nontemporal_load(q);
+        uint64_t hi = __builtin_nontemporal_load(q + 1);
+        int4 v;
+        v.x = (int32_t)lo; v.y = (int32_t)(lo >> 32);
+        v.z = (int32_t)hi; v.w = (int32_t)(hi >> 32);
+        return v;
+    };
+    uint64_t base = (uint64_t)blockIdx.x * blockDim.x + (uint64_t)wid * WAVE;
+    uint64_t i = base + lane;
+    for (; base + (K - 1) * stride + WAVE <= n4; base += K * stride, i += K * stride) {
+        int4 p[K];
+        #pragma unroll
+        for (int k = 0; k < K; k++) p[k] = ld4nt(pk4, i + k * stride);
+        #pragma unroll
+        for (int k = 0; k < K; k++) {
+            if (LEG == 0) {
+                acc += (unsigned long long)(uint32_t)(p[k].x + p[k].y + p[k].z + p[k].w);
+            } else {
+                while (n1 + 256 > Q1CAP) n1 -= 64;
+                #pragma unroll
+                for (int j = 0; j < 4; j++)
+                    push((&p[k].x)[j], (uint32_t)((i + k * stride) * 4 + j));
+            }
+        }
+        while (n1 >= 64) n1 -= 64;
+    }
+    // what Q1 holds at the end keeps its writes live
+    for (uint32_t w = lane; w < Q1CAP; w += WAVE)
+        acc += (unsigned long long)(uint32_t)(q1[wid][w].x + q1[wid][w].y);
+    for (int off = WAVE / 2; off > 0; off >>= 1)
+        acc += __shfl_down(acc, off, WAVE);
+    if (lane == 0 && acc) atomicAdd(sink, acc);
+}
+
 extern "C" int gpue_ubench_q21(gpue_session* s, int which, gpue_dbuf* pk, gpue_dbuf* sk,
                                gpue_dbuf* od, gpue_dbuf* rv, gpue_dbuf* pbits,
                                int64_t psmin, uint64_t psint, uint64_t n, int grid1024,
@@ -6867,6 +7287,16 @@ int gpue_ubench_q21(gpue_session* s, int which, gpue_dbuf* pk, gpue_dbuf* sk, gp
                 hipLaunchKernelGGL(k_ub_q21_phase1, dim3(grid1024), dim3(BLOCK_Q21), 0,
                                    s->stream, (const int4*)pk->ptr, n4, (const uint32_t*)pbits->ptr,
                                    psmin, psint, d_out);
+            } else if (which >= 4 && which <= 6) {
+                // push-path legs: pbits = fold A's 64 KB, then fold B's 32 KB
+                ARG_CHECK(which == 4 || (pbits && pbits->bytes >= (3u << 15)));
+                ARG_CHECK(n <= UINT32_MAX);
+                auto kern = which == 4 ? k_ub_q21_push<0> : which == 5 ? k_ub_q21_push<1>
+                                                                       : k_ub_q21_push<2>;
+                hipLaunchKernelGGL(kern, dim3(grid1024), dim3(BLOCK_Q21), 0, s->stream,
+                                   (const int32_t*)pk->ptr, n,
+                                   pbits ? (const uint32_t*)pbits->ptr : nullptr, psmin,
+                                   psint, d_out);
             } else if (which == 2 || which == 3) {
                 ARG_CHECK(sk && od && rv);
                 auto kern = which == 3 ? k_ub_q21_pf_legs<true> : k_ub_q21_pf_legs<false>;
