@@ -942,6 +942,131 @@ int gpue_group_agg_emit(gpue_session* s, gpue_group_agg* t, gpue_dbuf** out_keys
 int gpue_group_agg_reset(gpue_group_agg* t);
 void gpue_group_agg_destroy(gpue_group_agg* t);
 
+/* ---- general hash join: multi-key, NULL-aware, every join type ----------
+ * One persistent, growable join table beside the per-key-shape entries above
+ * (gpue_join_build_* / gpue_join_probe_emit_*, which stay as they are). It
+ * restates join_hash_map.h:228-333 (the per-join-type probes),
+ * join_hash_map_method.hpp (build and lookup) and join_key_constructor.h
+ * (multi-key handling: here the tuple is compared column by column instead of
+ * being serialised), and takes the nullable column format gpue_expr_project
+ * and gpue_group_agg_emit produce: a value column plus a u8 null column.
+ * Everything is exact (integers only).
+ *
+ * Keys: 1..GPUE_HJ_MAX_KEYS columns, each GPUE_PT_I32 or GPUE_PT_I64,
+ * declared separately for the build and the probe side. Values compare as
+ * sign-extended int64, so an int32 foreign key joins an int64 primary key.
+ * Every 64-bit pattern is a legal key; there is no sentinel. The null rules
+ * are those of gpue_group_agg_push: key_nulls (or an entry) may be NULL for a
+ * key declared nullable — no NULLs in this chunk; a non-NULL null buffer for
+ * a key declared non-nullable is GPUE_ERR_ARG; the cell under a NULL is never
+ * read into a hash or a compare. key_nullable covers both sides.
+ *
+ * Equality: a row that is NULL on a key with key_null_safe[i] == 0 matches
+ * nothing. With key_null_safe[i] == 1 (the <=> operator) NULL equals NULL and
+ * nothing else on that key. A build row that can match nothing is still a
+ * build row: it has an index, is never marked, and emit_build(matched = 0)
+ * reports it.
+ *
+ * Build: build_push may be called any number of times; build rows are
+ * numbered FROM 0 in push order across pushes (unlike the 1-based rows of the
+ * old entries). The table copies the keys, so the pushed buffers may be freed
+ * when the call returns. The table never fills: capacity_hint is a starting
+ * size, and before a push the slot array doubles on the device until load
+ * <= 5/8 even if every pushed row were a new tuple, re-inserting the occupied
+ * slots from the table's own key store (no host round trip over rows).
+ * n_rows == 0 is GPUE_OK. Total build rows stay below 2^32-1 (more is
+ * GPUE_ERR_ARG). A build_push after a probe is legal; existing marks persist.
+ * gpue_hash_join_stats reports {slot capacity, distinct matchable tuples,
+ * doublings of the slot array so far, re-insert passes so far}.
+ *
+ * Probe: emits (probe_idx, build_idx) as two u32 columns; probe_idx is
+ * relative to this call, build_idx is the global build row. Both outputs
+ * NULL: *count only (the count-then-emit protocol of the old entries). An
+ * output shorter than *count elements is GPUE_ERR_ARG, *count is set and
+ * nothing is written. out_probe_idx is non-decreasing; the order of one probe
+ * row's matches is unspecified.
+ *   INNER       every match
+ *   LEFT_SEMI   one pair per probe row with a match; which of its matches is
+ *               unspecified
+ *   LEFT_ANTI   (i, NO_ROW) per probe row without a match, rows with a NULL
+ *               key included
+ *   LEFT_OUTER  INNER plus (i, NO_ROW) for unmatched rows
+ *   NULL_AWARE_LEFT_ANTI  SQL NOT IN: over an empty build every probe row is
+ *               emitted, NULL ones too; else, if any build row has a NULL
+ *               key, nothing; else LEFT_ANTI without the NULL probe rows.
+ *               n_keys == 1 and a non-null-safe key only (else GPUE_ERR_ARG).
+ *               This differs on purpose from mode 6 of the old entries.
+ *   MARK_ONLY   emits nothing (*count = 0, outputs ignored), implies
+ *               GPUE_HJ_MARK_BUILD
+ * With GPUE_HJ_MARK_BUILD every build row that matched some probe row is
+ * marked in a bitmap the table keeps across probe calls (reset_marks clears
+ * it). A call takes at most 2^32-1 probe rows and one probe row at most
+ * 2^32-1 matches.
+ *
+ * RIGHT and FULL are compositions:
+ *   RIGHT OUTER  INNER probes with MARK_BUILD, then emit_build(matched = 0)
+ *   FULL OUTER   LEFT_OUTER probes with MARK_BUILD, then emit_build(0)
+ *   RIGHT SEMI   MARK_ONLY probes, then emit_build(1)
+ *   RIGHT ANTI   MARK_ONLY probes, then emit_build(0)
+ *
+ * emit_build writes the selected build rows in ascending index order. More
+ * than max_out of them: GPUE_ERR_ARG with *count the true count and nothing
+ * written. out NULL: *count only.
+ *
+ * gpue_gather_outer materialises a payload column through an index column
+ * that may hold NO_ROW: idx[j] == NO_ROW gives out[j] = 0, out_nulls[j] = 1;
+ * otherwise out[j] = in[idx[j]] and out_nulls[j] = in_nulls[idx[j]] (0 when
+ * in_nulls is NULL). width is the element size, 1, 4 or 8. out_nulls may be
+ * NULL only when the caller knows there is no NO_ROW and passes no in_nulls:
+ * a NO_ROW met without out_nulls is GPUE_ERR_ARG, and so is any other index
+ * >= in_rows — both reported through a device-side latch after the kernel,
+ * never by a fault (the rule gpue_window_eval states for order_idx); the
+ * outputs are then unspecified.
+ *
+ * GPUE_ERR_ARG, before any launch or allocation, for: n_keys outside
+ * 1..GPUE_HJ_MAX_KEYS, an unknown type, mode or flag, n_rows >= 2^32, a
+ * buffer shorter than n_rows (or max_out) elements, a missing key column,
+ * only one of the two probe outputs, outputs that overlap each other or an
+ * input.
+ *
+ * No lane waits on another lane's store: every device loop is a slot walk
+ * bounded by the capacity or a chain walk bounded by the tuple's row count,
+ * and a bound that is hit latches GPUE_ERR_HIP.
+ *
+ * Not covered: residual ("other") conjuncts evaluated inside the probe —
+ * filter the emitted pairs; varchar / float / decimal128 keys (the varchar
+ * entries above stay the route); more than 2^32-1 build rows; spilling. */
+typedef struct gpue_hash_join gpue_hash_join;
+#define GPUE_HJ_MAX_KEYS 4
+#define GPUE_HJ_NO_ROW 0xFFFFFFFFu      /* "no row on this side" in an index column */
+/* probe modes */
+#define GPUE_HJ_INNER 0
+#define GPUE_HJ_LEFT_SEMI 1
+#define GPUE_HJ_LEFT_ANTI 2
+#define GPUE_HJ_LEFT_OUTER 3
+#define GPUE_HJ_NULL_AWARE_LEFT_ANTI 4  /* NOT IN; n_keys == 1 only */
+#define GPUE_HJ_MARK_ONLY 5             /* emits nothing; implies GPUE_HJ_MARK_BUILD */
+/* probe flag */
+#define GPUE_HJ_MARK_BUILD 1            /* also mark every matched build row */
+int gpue_hash_join_create(gpue_session* s, const int32_t* build_key_type,
+                          const int32_t* probe_key_type, const int32_t* key_nullable,
+                          const int32_t* key_null_safe, int n_keys, uint64_t capacity_hint,
+                          gpue_hash_join** out);
+int gpue_hash_join_build_push(gpue_session* s, gpue_hash_join* t, gpue_dbuf** key_cols,
+                              gpue_dbuf** key_nulls, uint64_t n_rows);
+int gpue_hash_join_build_rows(gpue_hash_join* t, uint64_t* n_rows);
+int gpue_hash_join_stats(gpue_hash_join* t, uint64_t* out4);
+int gpue_hash_join_probe(gpue_session* s, gpue_hash_join* t, gpue_dbuf** key_cols,
+                         gpue_dbuf** key_nulls, uint64_t n_rows, int mode, int flags,
+                         gpue_dbuf* out_probe_idx, gpue_dbuf* out_build_idx, uint64_t* count);
+int gpue_hash_join_emit_build(gpue_session* s, gpue_hash_join* t, int matched /* 1 or 0 */,
+                              gpue_dbuf* out_build_idx, uint64_t max_out, uint64_t* count);
+int gpue_hash_join_reset_marks(gpue_session* s, gpue_hash_join* t);
+void gpue_hash_join_destroy(gpue_hash_join* t);
+int gpue_gather_outer(gpue_session* s, gpue_dbuf* in, gpue_dbuf* in_nulls /* or NULL */,
+                      uint64_t in_rows, int width /* 1, 4, 8 */, gpue_dbuf* idx, uint64_t n,
+                      gpue_dbuf* out, gpue_dbuf* out_nulls /* or NULL */);
+
 /* ---- pinned double-buffered H2D ingest ----
  * north_star's "columnar batches pinned and streamed to HBM": two
  * hipHostMalloc staging buffers on the session's second stream; while chunk

@@ -8822,6 +8822,639 @@ int gpue_group_agg_emit(gpue_session* s, gpue_group_agg* t, gpue_dbuf** out_keys
 }
 
 // ---------------------------------------------------------------------------
+// General hash join (gpue_hash_join_*, gpue.h "general hash join"; DESIGN.md
+// §4j): 1..4 int32/int64 key columns with NULLs and per-key null-safe
+// equality, a build side pushed in any number of chunks, every join type.
+//
+// The table owns a row store, appended per push by k_hj_store: the canonical
+// int64 key tuple (0 under NULL), one byte of null flags, and three u32 per
+// row — rep (the first row that carried this tuple, NO_ROW for a row that can
+// match nothing), cnt (on a rep row: how many rows carry its tuple) and next
+// (the chain of those rows, starting at the rep). k_hj_insert then resolves
+// each new row to its rep through an open-addressed array of distinct-tuple
+// slots. The slot word is group_agg's without the FRESH state: 0 = EMPTY, else
+// bit 63 | 4 null flags | 26-bit fingerprint | the rep's row index, claimed by
+// one 64-bit CAS. A lane that finds an occupied slot with its tag compares
+// against the key store at the rep's row, which k_hj_store — an earlier
+// kernel — wrote: nothing a key compare reads is written during the kernel, so
+// no lane waits on another lane's store. Equal rows link behind the rep with
+// next[row] = atomicExch(&next[rep], row).
+//
+// A probe row finds its rep with one tuple compare per tag hit and reads
+// cnt[rep]: counting, SEMI, ANTI and marking never touch the chain. Marks are
+// one bit per rep row; a build row is matched iff its rep's bit is set. Only
+// the INNER / OUTER emit walks next[], cnt[rep] steps, one index load per
+// emitted pair. Every loop is a slot walk bounded by the capacity or a chain
+// walk bounded by cnt[rep]; either bound latches an error instead of spinning.
+// ---------------------------------------------------------------------------
+static constexpr uint32_t HJ_NO_ROW = GPUE_HJ_NO_ROW;
+static constexpr uint64_t HJ_MIN_CAP = 16;
+static constexpr uint64_t HJ_MAX_CAP = 1ull << 34;
+#define HJ_ERR_WALK 1ull   /* a bounded slot or chain walk hit its bound */
+#define AGG_ERR_GATHER_IDX 8u    /* gather_outer: an index >= in_rows */
+#define AGG_ERR_GATHER_NOROW 16u /* gather_outer: NO_ROW without out_nulls */
+
+struct HjTable {
+    unsigned long long* slots; // cap words
+    uint64_t cap;              // power of two
+    long long* kstore;         // [row * n_keys + key], 0 under NULL
+    uint8_t* knull;            // bit k = NULL on key k
+    uint32_t *next, *rep, *cnt;
+    uint32_t* marks;           // one bit per row, set on rep rows only
+    uint32_t n_keys, ns_mask;  // ns_mask bit k = key k is null-safe
+};
+
+__device__ static inline GaKey hj_store_key(const HjTable& t, uint64_t row, uint32_t nb) {
+    GaKey k;
+    k.nb = nb;
+#pragma unroll
+    for (int c = 0; c < GPUE_HJ_MAX_KEYS; c++)
+        k.v[c] = c < (int)t.n_keys ? t.kstore[row * t.n_keys + c] : 0;
+    return k;
+}
+
+// ctl[0] = distinct tuples in the slots, ctl[1] = error latch, ctl[2] = some
+// build row is NULL on a key that is not null-safe
+__global__ void k_hj_store(const HjTable t, const GaInput in, uint64_t base, uint64_t n,
+                           unsigned long long* __restrict__ ctl) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const GaKey k = ga_load_key(in, t.n_keys, i);
+        const uint64_t row = base + i;
+#pragma unroll
+        for (int c = 0; c < GPUE_HJ_MAX_KEYS; c++)
+            if (c < (int)t.n_keys) t.kstore[row * t.n_keys + c] = k.v[c];
+        t.knull[row] = (uint8_t)k.nb;
+        t.next[row] = HJ_NO_ROW;
+        t.rep[row] = HJ_NO_ROW;
+        t.cnt[row] = 0;
+        if ((k.nb & ~t.ns_mask) && *(volatile unsigned long long*)&ctl[2] == 0)
+            atomicOr(&ctl[2], 1ull);
+    }
+}
+
+// the slot walk both sides share: the rep row of tuple k, or NO_ROW at the
+// first EMPTY slot. claim != NO_ROW: CAS that row in as the rep instead.
+__device__ static inline uint32_t hj_find(const HjTable& t, const GaKey& k, uint32_t claim,
+                                          bool* claimed, unsigned long long* ctl) {
+    const uint64_t mask = t.cap - 1;
+    const uint64_t h = ga_hash(k, t.n_keys);
+    const unsigned long long fp = ga_tag(h, k.nb);
+    uint64_t s = h & mask, left = t.cap;
+    for (;;) {
+        unsigned long long cur = t.slots[s];
+        if (cur == 0) {
+            if (claim == HJ_NO_ROW) return HJ_NO_ROW;
+            cur = atomicCAS(&t.slots[s], 0ull, GA_OCC | fp | claim);
+            if (cur == 0) { *claimed = true; return claim; }
+        }
+        if ((cur & GA_FP_MASK) == fp) { // null flags equal: they are part of the tag
+            const uint32_t r = (uint32_t)cur;
+            if (ga_key_eq(k, hj_store_key(t, r, k.nb))) return r;
+        }
+        s = (s + 1) & mask;
+        if (--left == 0) { atomicOr(&ctl[1], HJ_ERR_WALK); return HJ_NO_ROW; }
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void
+k_hj_insert(const HjTable t, uint64_t base, uint64_t n, unsigned long long* __restrict__ ctl) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t b0 = (uint64_t)blockIdx.x * blockDim.x; b0 < n; b0 += stride) {
+        const uint64_t i = b0 + threadIdx.x;
+        bool claimed = false;
+        if (i < n) {
+            const uint64_t row = base + i;
+            const uint32_t nb = t.knull[row];
+            if (!(nb & ~t.ns_mask)) {
+                const GaKey k = hj_store_key(t, row, nb);
+                const uint32_t r = hj_find(t, k, (uint32_t)row, &claimed, ctl);
+                if (r != HJ_NO_ROW) {
+                    t.rep[row] = r;
+                    atomicAdd(&t.cnt[r], 1u);
+                    if (r != (uint32_t)row) t.next[row] = atomicExch(&t.next[r], (uint32_t)row);
+                }
+            }
+        }
+        const uint64_t cm = __ballot(claimed);
+        if (cm && (threadIdx.x & (WAVE - 1)) == __ffsll((unsigned long long)cm) - 1)
+            atomicAdd(&ctl[0], (unsigned long long)__popcll(cm));
+    }
+}
+
+// growth: the occupied words move as they are (tag and rep row); the hash is
+// re-derived from the key store at the rep row. Old tuples are distinct, so
+// the claim needs no compare.
+__global__ void k_hj_rehash(const unsigned long long* __restrict__ old_slots, uint64_t old_cap,
+                            const HjTable nt, unsigned long long* __restrict__ ctl) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t mask = nt.cap - 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_cap;
+         i += stride) {
+        const unsigned long long w = old_slots[i];
+        if (w == 0) continue;
+        const GaKey k = hj_store_key(nt, (uint32_t)w, (uint32_t)(w >> GA_NB_SHIFT) & 0xFu);
+        uint64_t s = ga_hash(k, nt.n_keys) & mask, left = nt.cap;
+        while (atomicCAS(&nt.slots[s], 0ull, w) != 0) {
+            s = (s + 1) & mask;
+            if (--left == 0) { atomicOr(&ctl[1], HJ_ERR_WALK); break; }
+        }
+    }
+}
+
+// per probe row: its rep (kept for the emit pass) and the count its mode emits
+__global__ __launch_bounds__(BLOCK) void
+k_hj_probe_count(const HjTable t, const GaInput in, uint64_t n, int mode, int skip_nulls,
+                 int mark, uint32_t* __restrict__ reps, uint32_t* __restrict__ counts,
+                 unsigned long long* __restrict__ ctl) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const GaKey k = ga_load_key(in, t.n_keys, i);
+        uint32_t r = HJ_NO_ROW;
+        if (!(k.nb & ~t.ns_mask)) r = hj_find(t, k, HJ_NO_ROW, nullptr, ctl);
+        if (mode == GPUE_HJ_MARK_ONLY) {
+            if (r != HJ_NO_ROW && !(t.marks[r >> 5] >> (r & 31) & 1u))
+                atomicOr(&t.marks[r >> 5], 1u << (r & 31));
+            continue;
+        }
+        const uint32_t c = r == HJ_NO_ROW ? 0u : t.cnt[r];
+        if (mark && c && !(t.marks[r >> 5] >> (r & 31) & 1u))
+            atomicOr(&t.marks[r >> 5], 1u << (r & 31));
+        reps[i] = r;
+        counts[i] = (skip_nulls && k.nb) ? 0u : join_mode_count(c, mode);
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void
+k_hj_probe_emit(const HjTable t, uint64_t n, int mode, const uint32_t* __restrict__ reps,
+                const uint32_t* __restrict__ counts, const uint64_t* __restrict__ offsets,
+                uint32_t* __restrict__ out_probe, uint32_t* __restrict__ out_build,
+                unsigned long long* __restrict__ ctl) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t c = counts[i];
+        if (c == 0) continue;
+        uint64_t o = offsets[i];
+        uint32_t b = reps[i];
+        if (b == HJ_NO_ROW || mode == GPUE_HJ_LEFT_SEMI || mode == GPUE_HJ_LEFT_ANTI) {
+            out_probe[o] = (uint32_t)i;
+            out_build[o] = mode == GPUE_HJ_LEFT_SEMI ? b : HJ_NO_ROW;
+            continue;
+        }
+        // c == cnt[rep]: the chain holds exactly c rows, the rep first
+        for (uint32_t j = 0; j < c; j++, o++) {
+            if (b == HJ_NO_ROW) { atomicOr(&ctl[1], HJ_ERR_WALK); b = reps[i]; }
+            out_probe[o] = (uint32_t)i;
+            out_build[o] = b;
+            b = t.next[b];
+        }
+    }
+}
+
+// emit_build: 1 for the build rows selected (matched, or not matched)
+__global__ void k_hj_build_counts(const HjTable t, uint64_t rows, int matched,
+                                  uint32_t* __restrict__ counts) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < rows; j += stride) {
+        const uint32_t r = t.rep[j];
+        const uint32_t m = r == HJ_NO_ROW ? 0u : (t.marks[r >> 5] >> (r & 31)) & 1u;
+        counts[j] = matched ? m : 1u - m;
+    }
+}
+
+__global__ void k_hj_build_emit(const uint32_t* __restrict__ counts,
+                                const uint64_t* __restrict__ offsets, uint64_t rows,
+                                uint32_t* __restrict__ out_build) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < rows; j += stride)
+        if (counts[j]) out_build[offsets[j]] = (uint32_t)j;
+}
+
+template <class T>
+__global__ void k_gather_outer(const T* __restrict__ in, const uint8_t* __restrict__ in_nulls,
+                               uint64_t in_rows, const uint32_t* __restrict__ idx, uint64_t n,
+                               T* __restrict__ out, uint8_t* __restrict__ out_nulls,
+                               unsigned int* __restrict__ err) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
+        const uint32_t r = idx[j];
+        T v = 0;
+        uint8_t nl = 1;
+        if (r == HJ_NO_ROW) {
+            if (!out_nulls) atomicOr(err, AGG_ERR_GATHER_NOROW);
+        } else if (r >= in_rows) {
+            atomicOr(err, AGG_ERR_GATHER_IDX); // never dereferenced
+        } else {
+            v = in[r];
+            nl = in_nulls ? (in_nulls[r] != 0) : 0;
+        }
+        out[j] = v;
+        if (out_nulls) out_nulls[j] = nl;
+    }
+}
+
+struct gpue_hash_join {
+    gpue_session* s = nullptr;
+    int n_keys = 0;
+    int32_t btype[GPUE_HJ_MAX_KEYS] = {}, ptype[GPUE_HJ_MAX_KEYS] = {};
+    int32_t nullable[GPUE_HJ_MAX_KEYS] = {}, null_safe[GPUE_HJ_MAX_KEYS] = {};
+    HjTable d = {};
+    uint64_t rows = 0, rows_cap = 0;
+    unsigned long long* ctl = nullptr; // [0] distinct tuples, [1] error latch, [2] NULL build row
+    uint64_t distinct = 0;
+    bool has_null_row = false;
+    uint64_t doublings = 0, rehashes = 0;
+};
+
+static void hj_free_rows(HjTable& d) {
+    (void)hipFree(d.kstore); (void)hipFree(d.knull); (void)hipFree(d.next);
+    (void)hipFree(d.rep); (void)hipFree(d.cnt); (void)hipFree(d.marks);
+    d.kstore = nullptr; d.knull = nullptr; d.next = d.rep = d.cnt = d.marks = nullptr;
+}
+
+static inline uint64_t hj_mark_bytes(uint64_t rows_cap) { return (rows_cap + 31) / 32 * 4; }
+
+// the row store holds `rows` more rows: doubles, copying device to device
+static int hj_reserve_rows(gpue_hash_join* t, uint64_t rows) {
+    if (rows <= t->rows_cap) return GPUE_OK;
+    uint64_t cap = std::max<uint64_t>(t->rows_cap * 2, 1024);
+    while (cap < rows) cap <<= 1;
+    gpue_session* s = t->s;
+    HjTable nd = t->d;
+    nd.kstore = nullptr; nd.knull = nullptr; nd.next = nd.rep = nd.cnt = nd.marks = nullptr;
+    hipError_t e = hipMalloc(&nd.kstore, cap * 8 * t->n_keys);
+    if (e == hipSuccess) e = hipMalloc(&nd.knull, cap);
+    if (e == hipSuccess) e = hipMalloc(&nd.next, cap * 4);
+    if (e == hipSuccess) e = hipMalloc(&nd.rep, cap * 4);
+    if (e == hipSuccess) e = hipMalloc(&nd.cnt, cap * 4);
+    if (e == hipSuccess) e = hipMalloc(&nd.marks, hj_mark_bytes(cap));
+    if (e == hipSuccess) e = hipMemsetAsync(nd.marks, 0, hj_mark_bytes(cap), s->stream);
+    const uint64_t r = t->rows;
+    auto cp = [&](void* dst, const void* src, uint64_t bytes) {
+        if (e == hipSuccess && bytes)
+            e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->stream);
+    };
+    cp(nd.kstore, t->d.kstore, r * 8 * t->n_keys);
+    cp(nd.knull, t->d.knull, r);
+    cp(nd.next, t->d.next, r * 4);
+    cp(nd.rep, t->d.rep, r * 4);
+    cp(nd.cnt, t->d.cnt, r * 4);
+    cp(nd.marks, t->d.marks, r ? hj_mark_bytes(t->rows_cap) : 0);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) {
+        hj_free_rows(nd);
+        snprintf(g_err, sizeof(g_err), "hash_join: row store of %llu rows: %s",
+                 (unsigned long long)cap, hipGetErrorString(e));
+        return GPUE_ERR_HIP;
+    }
+    hj_free_rows(t->d);
+    t->d.kstore = nd.kstore; t->d.knull = nd.knull; t->d.next = nd.next;
+    t->d.rep = nd.rep; t->d.cnt = nd.cnt; t->d.marks = nd.marks;
+    t->rows_cap = cap;
+    return GPUE_OK;
+}
+
+// the slot array keeps load <= 5/8 even if every one of `additional` rows is a
+// new tuple: doubles until it does and re-inserts the occupied words on device
+static int hj_ensure_slots(gpue_hash_join* t, uint64_t additional) {
+    const uint64_t need = t->distinct + additional;
+    if (need + need / 2 <= t->d.cap) return GPUE_OK;
+    uint64_t ncap = t->d.cap, dbl = 0;
+    while (need + need / 2 > ncap) { ncap <<= 1; dbl++; }
+    if (ncap > HJ_MAX_CAP) {
+        snprintf(g_err, sizeof(g_err), "hash_join: %llu tuples exceed the table limit",
+                 (unsigned long long)need);
+        return GPUE_ERR_ARG;
+    }
+    gpue_session* s = t->s;
+    HjTable nd = t->d;
+    nd.cap = ncap;
+    nd.slots = nullptr;
+    hipError_t e = hipMalloc(&nd.slots, ncap * 8);
+    if (e == hipSuccess) e = hipMemsetAsync(nd.slots, 0, ncap * 8, s->stream);
+    bool walk = false;
+    if (e == hipSuccess && t->distinct) {
+        hipLaunchKernelGGL(k_hj_rehash, dim3(grid_for(t->d.cap)), dim3(BLOCK), 0, s->stream,
+                           (const unsigned long long*)t->d.slots, t->d.cap, nd, t->ctl);
+        e = hipGetLastError();
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(s->pinned, t->ctl, 24, hipMemcpyDeviceToHost, s->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+        walk = e == hipSuccess && ((const volatile unsigned long long*)s->pinned)[1] != 0;
+        t->rehashes++;
+    } else if (e == hipSuccess) {
+        e = hipStreamSynchronize(s->stream);
+    }
+    if (e != hipSuccess || walk) {
+        if (walk) (void)hipMemsetAsync(t->ctl + 1, 0, 8, s->stream);
+        (void)hipStreamSynchronize(s->stream);
+        (void)hipFree(nd.slots);
+        snprintf(g_err, sizeof(g_err), "hash_join: growth to %llu slots failed: %s",
+                 (unsigned long long)ncap,
+                 e != hipSuccess ? hipGetErrorString(e) : "bounded walk exhausted");
+        return GPUE_ERR_HIP;
+    }
+    (void)hipFree(t->d.slots);
+    t->d.slots = nd.slots;
+    t->d.cap = ncap;
+    t->doublings += dbl;
+    return GPUE_OK;
+}
+
+// read ctl after a kernel; clears and reports the walk latch
+static int hj_read_ctl(gpue_hash_join* t, const char* what) {
+    gpue_session* s = t->s;
+    HIP_CHECK(hipMemcpyAsync(s->pinned, t->ctl, 24, hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    const volatile unsigned long long* c = (const volatile unsigned long long*)s->pinned;
+    t->distinct = c[0];
+    t->has_null_row = c[2] != 0;
+    if (c[1]) {
+        HIP_CHECK(hipMemsetAsync(t->ctl + 1, 0, 8, s->stream));
+        HIP_CHECK(hipStreamSynchronize(s->stream));
+        snprintf(g_err, sizeof(g_err), "%s: a bounded table walk hit its bound", what);
+        return GPUE_ERR_HIP;
+    }
+    return GPUE_OK;
+}
+
+int gpue_hash_join_create(gpue_session* s, const int32_t* build_key_type,
+                          const int32_t* probe_key_type, const int32_t* key_nullable,
+                          const int32_t* key_null_safe, int n_keys, uint64_t capacity_hint,
+                          gpue_hash_join** out) {
+    ARG_CHECK(s && out && build_key_type && probe_key_type && key_nullable && key_null_safe);
+    ARG_CHECK(n_keys >= 1 && n_keys <= GPUE_HJ_MAX_KEYS);
+    for (int k = 0; k < n_keys; k++) {
+        ARG_CHECK(build_key_type[k] == GPUE_PT_I32 || build_key_type[k] == GPUE_PT_I64);
+        ARG_CHECK(probe_key_type[k] == GPUE_PT_I32 || probe_key_type[k] == GPUE_PT_I64);
+    }
+    std::unique_ptr<gpue_hash_join> t(new gpue_hash_join());
+    t->s = s;
+    t->n_keys = n_keys;
+    t->d.n_keys = n_keys;
+    for (int k = 0; k < n_keys; k++) {
+        t->btype[k] = build_key_type[k];
+        t->ptype[k] = probe_key_type[k];
+        t->nullable[k] = key_nullable[k] != 0;
+        t->null_safe[k] = key_null_safe[k] != 0;
+        if (t->null_safe[k]) t->d.ns_mask |= 1u << k;
+    }
+    uint64_t cap = HJ_MIN_CAP;
+    while (cap < capacity_hint + capacity_hint / 2 && cap < HJ_MAX_CAP) cap <<= 1;
+    t->d.cap = cap;
+    HIP_CHECK(hipSetDevice(s->device));
+    hipError_t e = hipMalloc(&t->ctl, 3 * 8);
+    if (e == hipSuccess) e = hipMemsetAsync(t->ctl, 0, 3 * 8, s->stream);
+    if (e == hipSuccess) e = hipMalloc(&t->d.slots, cap * 8);
+    if (e == hipSuccess) e = hipMemsetAsync(t->d.slots, 0, cap * 8, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) {
+        snprintf(g_err, sizeof(g_err), "hash_join_create: %s", hipGetErrorString(e));
+        gpue_hash_join_destroy(t.release());
+        return GPUE_ERR_HIP;
+    }
+    *out = t.release();
+    return GPUE_OK;
+}
+
+void gpue_hash_join_destroy(gpue_hash_join* t) {
+    if (!t) return;
+    hj_free_rows(t->d);
+    (void)hipFree(t->d.slots);
+    (void)hipFree(t->ctl);
+    delete t;
+}
+
+// validates one side's key columns and binds them; width by that side's types
+static int hj_bind_keys(const gpue_hash_join* t, const int32_t* types, gpue_dbuf** key_cols,
+                        gpue_dbuf** key_nulls, uint64_t n_rows, GaInput* in) {
+    memset(in, 0, sizeof(*in));
+    ARG_CHECK(key_cols);
+    for (int k = 0; k < t->n_keys; k++) {
+        const uint64_t w = types[k] == GPUE_PT_I64 ? 8 : 4;
+        ARG_CHECK(key_cols[k] != nullptr);
+        ARG_CHECK(key_cols[k]->bytes >= n_rows * w);
+        gpue_dbuf* nl = key_nulls ? key_nulls[k] : nullptr;
+        if (nl) {
+            ARG_CHECK(t->nullable[k]); // null buffer for a key declared NOT NULL
+            ARG_CHECK(nl->bytes >= n_rows);
+        }
+        in->kcol[k] = key_cols[k]->ptr;
+        in->knul[k] = nl ? (const uint8_t*)nl->ptr : nullptr;
+        in->k64[k] = w == 8;
+    }
+    return GPUE_OK;
+}
+
+int gpue_hash_join_build_push(gpue_session* s, gpue_hash_join* t, gpue_dbuf** key_cols,
+                              gpue_dbuf** key_nulls, uint64_t n_rows) {
+    ARG_CHECK(s && t);
+    ARG_CHECK(n_rows < (1ull << 32));
+    ARG_CHECK(t->rows + n_rows < (uint64_t)HJ_NO_ROW); // row indexes stay below NO_ROW
+    GaInput in;
+    int rc = hj_bind_keys(t, t->btype, key_cols, key_nulls, n_rows, &in);
+    if (rc != GPUE_OK) return rc;
+    if (n_rows == 0) return GPUE_OK;
+    HIP_CHECK(hipSetDevice(s->device));
+    rc = hj_reserve_rows(t, t->rows + n_rows);
+    if (rc == GPUE_OK) rc = hj_ensure_slots(t, n_rows);
+    if (rc != GPUE_OK) return rc;
+    hipLaunchKernelGGL(k_hj_store, dim3(grid_for(n_rows)), dim3(BLOCK), 0, s->stream, t->d, in,
+                       t->rows, n_rows, t->ctl);
+    HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(k_hj_insert, dim3(grid_for(n_rows)), dim3(BLOCK), 0, s->stream, t->d,
+                       t->rows, n_rows, t->ctl);
+    HIP_CHECK(hipGetLastError());
+    t->rows += n_rows; // the rows are in the store whatever the insert reports
+    return hj_read_ctl(t, "hash_join_build_push"); // syncs: the caller's buffers are free
+}
+
+int gpue_hash_join_build_rows(gpue_hash_join* t, uint64_t* n_rows) {
+    ARG_CHECK(t && n_rows);
+    *n_rows = t->rows;
+    return GPUE_OK;
+}
+
+int gpue_hash_join_stats(gpue_hash_join* t, uint64_t* out4) {
+    ARG_CHECK(t && out4);
+    out4[0] = t->d.cap;
+    out4[1] = t->distinct;
+    out4[2] = t->doublings;
+    out4[3] = t->rehashes;
+    return GPUE_OK;
+}
+
+static inline bool hj_overlap(const gpue_dbuf* x, const gpue_dbuf* y) {
+    const char *xa = (const char*)x->ptr, *ya = (const char*)y->ptr;
+    return xa < ya + y->bytes && ya < xa + x->bytes;
+}
+
+int gpue_hash_join_probe(gpue_session* s, gpue_hash_join* t, gpue_dbuf** key_cols,
+                         gpue_dbuf** key_nulls, uint64_t n_rows, int mode, int flags,
+                         gpue_dbuf* out_probe_idx, gpue_dbuf* out_build_idx, uint64_t* count) {
+    ARG_CHECK(s && t && count);
+    ARG_CHECK(mode >= GPUE_HJ_INNER && mode <= GPUE_HJ_MARK_ONLY);
+    ARG_CHECK(flags == 0 || flags == GPUE_HJ_MARK_BUILD);
+    ARG_CHECK(n_rows < (1ull << 32));
+    if (mode == GPUE_HJ_NULL_AWARE_LEFT_ANTI) ARG_CHECK(t->n_keys == 1 && !t->null_safe[0]);
+    ARG_CHECK((out_probe_idx == nullptr) == (out_build_idx == nullptr));
+    GaInput in;
+    int rc = hj_bind_keys(t, t->ptype, key_cols, key_nulls, n_rows, &in);
+    if (rc != GPUE_OK) return rc;
+    if (out_probe_idx && mode != GPUE_HJ_MARK_ONLY) {
+        ARG_CHECK(!hj_overlap(out_probe_idx, out_build_idx)); // outputs overlap
+        for (int k = 0; k < t->n_keys; k++) {
+            ARG_CHECK(!hj_overlap(out_probe_idx, key_cols[k]) &&
+                      !hj_overlap(out_build_idx, key_cols[k]));
+            if (in.knul[k])
+                ARG_CHECK(!hj_overlap(out_probe_idx, key_nulls[k]) &&
+                          !hj_overlap(out_build_idx, key_nulls[k]));
+        }
+    }
+    *count = 0;
+    if (n_rows == 0) return GPUE_OK;
+    int kmode = mode, skip_nulls = 0;
+    if (mode == GPUE_HJ_NULL_AWARE_LEFT_ANTI) {
+        // NOT IN: over an empty build every row passes, NULL ones too; a NULL
+        // in the build makes every comparison unknown; else NULL rows drop
+        kmode = GPUE_HJ_LEFT_ANTI;
+        if (t->rows && t->has_null_row) return GPUE_OK;
+        skip_nulls = t->rows != 0;
+    }
+    const int mark = mode == GPUE_HJ_MARK_ONLY || flags == GPUE_HJ_MARK_BUILD;
+    HIP_CHECK(hipSetDevice(s->device));
+    if (t->rows_cap == 0) { // an empty build still needs a mark word to point at
+        rc = hj_reserve_rows(t, 1);
+        if (rc != GPUE_OK) return rc;
+    }
+    if (mode == GPUE_HJ_MARK_ONLY) {
+        hipLaunchKernelGGL(k_hj_probe_count, dim3(grid_for(n_rows)), dim3(BLOCK), 0, s->stream,
+                           t->d, in, n_rows, mode, 0, 1, (uint32_t*)nullptr,
+                           (uint32_t*)nullptr, t->ctl);
+        HIP_CHECK(hipGetLastError());
+        return hj_read_ctl(t, "hash_join_probe");
+    }
+    DevScratch own;
+    uint32_t* d_reps = nullptr;
+    HIP_CHECK(own.alloc(&d_reps, n_rows * 4));
+    const HjTable d = t->d;
+    unsigned long long* ctl = t->ctl;
+    rc = probe_count_scan_emit(
+        s, n_rows, out_probe_idx, out_build_idx, count,
+        [&](uint32_t nb, uint32_t* d_counts) {
+            hipLaunchKernelGGL(k_hj_probe_count, dim3(nb), dim3(BLOCK), 0, s->stream, d, in,
+                               n_rows, kmode, skip_nulls, mark, d_reps, d_counts, ctl);
+        },
+        [&](uint32_t nb, const uint32_t* d_counts, const uint64_t* d_offsets,
+            uint32_t* out_probe, uint32_t* out_build) {
+            hipLaunchKernelGGL(k_hj_probe_emit, dim3(nb), dim3(BLOCK), 0, s->stream, d, n_rows,
+                               kmode, (const uint32_t*)d_reps, d_counts, d_offsets, out_probe,
+                               out_build, ctl);
+        });
+    if (rc != GPUE_OK) {
+        (void)hipStreamSynchronize(s->stream); // the scratch is freed on return
+        return rc;
+    }
+    return hj_read_ctl(t, "hash_join_probe");
+}
+
+int gpue_hash_join_emit_build(gpue_session* s, gpue_hash_join* t, int matched,
+                              gpue_dbuf* out_build_idx, uint64_t max_out, uint64_t* count) {
+    ARG_CHECK(s && t && count);
+    ARG_CHECK(matched == 0 || matched == 1);
+    ARG_CHECK(max_out < (1ull << 32));
+    if (out_build_idx) ARG_CHECK(out_build_idx->bytes >= max_out * 4);
+    *count = 0;
+    const uint64_t br = t->rows;
+    if (br == 0) return GPUE_OK;
+    HIP_CHECK(hipSetDevice(s->device));
+    DevScratch tmp;
+    CountScan scan;
+    uint32_t* d_counts = nullptr;
+    uint64_t* d_offsets = nullptr;
+    const uint32_t nb = grid_for(br);
+    HIP_CHECK(tmp.alloc(&d_counts, br * 4));
+    int rc = scan.init(s, tmp, br);
+    if (rc != GPUE_OK) return rc;
+    hipLaunchKernelGGL(k_hj_build_counts, dim3(nb), dim3(BLOCK), 0, s->stream, t->d, br, matched,
+                       d_counts);
+    uint64_t total = 0;
+    rc = scan.total(d_counts, &total);
+    if (rc != GPUE_OK) return rc;
+    *count = total;
+    if (!out_build_idx || total == 0) return GPUE_OK;
+    if (total > max_out) {
+        snprintf(g_err, sizeof(g_err), "hash_join_emit_build: %llu rows exceed max_out %llu",
+                 (unsigned long long)total, (unsigned long long)max_out);
+        return GPUE_ERR_ARG;
+    }
+    HIP_CHECK(tmp.alloc(&d_offsets, br * 8));
+    scan.offsets(d_offsets);
+    hipLaunchKernelGGL(k_hj_build_emit, dim3(nb), dim3(BLOCK), 0, s->stream,
+                       (const uint32_t*)d_counts, (const uint64_t*)d_offsets, br,
+                       (uint32_t*)out_build_idx->ptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GPUE_OK;
+}
+
+int gpue_hash_join_reset_marks(gpue_session* s, gpue_hash_join* t) {
+    ARG_CHECK(s && t);
+    if (t->rows_cap == 0) return GPUE_OK;
+    HIP_CHECK(hipSetDevice(s->device));
+    HIP_CHECK(hipMemsetAsync(t->d.marks, 0, hj_mark_bytes(t->rows_cap), s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    return GPUE_OK;
+}
+
+int gpue_gather_outer(gpue_session* s, gpue_dbuf* in, gpue_dbuf* in_nulls, uint64_t in_rows,
+                      int width, gpue_dbuf* idx, uint64_t n, gpue_dbuf* out,
+                      gpue_dbuf* out_nulls) {
+    ARG_CHECK(s && in && idx && out);
+    ARG_CHECK(width == 1 || width == 4 || width == 8);
+    ARG_CHECK(n < (1ull << 32) && in_rows < (1ull << 32));
+    ARG_CHECK(in->bytes >= in_rows * (uint64_t)width);
+    ARG_CHECK(!in_nulls || in_nulls->bytes >= in_rows);
+    ARG_CHECK(!in_nulls || out_nulls); // the input's NULLs need somewhere to go
+    ARG_CHECK(idx->bytes >= n * 4 && out->bytes >= n * (uint64_t)width);
+    ARG_CHECK(!out_nulls || out_nulls->bytes >= n);
+    ARG_CHECK(!hj_overlap(out, in) && !hj_overlap(out, idx));
+    if (in_nulls) ARG_CHECK(!hj_overlap(out, in_nulls) && !hj_overlap(out_nulls, in_nulls));
+    if (out_nulls)
+        ARG_CHECK(!hj_overlap(out_nulls, out) && !hj_overlap(out_nulls, in) &&
+                  !hj_overlap(out_nulls, idx));
+    if (n == 0) return GPUE_OK;
+    HIP_CHECK(hipSetDevice(s->device));
+    const uint8_t* inl = in_nulls ? (const uint8_t*)in_nulls->ptr : nullptr;
+    uint8_t* onl = out_nulls ? (uint8_t*)out_nulls->ptr : nullptr;
+    const uint32_t* ix = (const uint32_t*)idx->ptr;
+    const dim3 g(grid_for(n)), b(BLOCK);
+    if (width == 1)
+        hipLaunchKernelGGL(k_gather_outer<uint8_t>, g, b, 0, s->stream, (const uint8_t*)in->ptr,
+                           inl, in_rows, ix, n, (uint8_t*)out->ptr, onl, s->d_agg_err);
+    else if (width == 4)
+        hipLaunchKernelGGL(k_gather_outer<uint32_t>, g, b, 0, s->stream,
+                           (const uint32_t*)in->ptr, inl, in_rows, ix, n, (uint32_t*)out->ptr,
+                           onl, s->d_agg_err);
+    else
+        hipLaunchKernelGGL(k_gather_outer<uint64_t>, g, b, 0, s->stream,
+                           (const uint64_t*)in->ptr, inl, in_rows, ix, n, (uint64_t*)out->ptr,
+                           onl, s->d_agg_err);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(s->pinned, s->d_agg_err, 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    const unsigned int err = *(const volatile unsigned int*)s->pinned;
+    if (err & (AGG_ERR_GATHER_IDX | AGG_ERR_GATHER_NOROW)) {
+        HIP_CHECK(hipMemset(s->d_agg_err, 0, sizeof(unsigned int)));
+        snprintf(g_err, sizeof(g_err), "gather_outer: %s",
+                 err & AGG_ERR_GATHER_IDX ? "idx holds an index >= in_rows"
+                                          : "idx holds NO_ROW and there is no out_nulls");
+        return GPUE_ERR_ARG;
+    }
+    return GPUE_OK;
+}
+
+// ---------------------------------------------------------------------------
 // Config 5 — TPC-H Q3-shaped: lineitem ⋈ orders ⋈ customer with a 16-byte
 // dictionary-string filter (SERIALIZED_FIXED_SIZE_LARGEINT packing: two u64
 // compares — reference join_hash_table.cpp:185-192), decimal revenue as

@@ -210,6 +210,20 @@ def _declare(lib):
                                 [c_u64, ctypes.POINTER(c_u64)]),
         "gpue_group_agg_reset": (c_i32, [c_vp]),
         "gpue_group_agg_destroy": (None, [c_vp]),
+        "gpue_hash_join_create": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_u64,
+                                          ctypes.POINTER(c_vp)]),
+        "gpue_hash_join_build_push": (c_i32, [c_vp, c_vp] + [ctypes.POINTER(c_vp)] * 2 +
+                                      [c_u64]),
+        "gpue_hash_join_build_rows": (c_i32, [c_vp, ctypes.POINTER(c_u64)]),
+        "gpue_hash_join_stats": (c_i32, [c_vp, c_vp]),
+        "gpue_hash_join_probe": (c_i32, [c_vp, c_vp] + [ctypes.POINTER(c_vp)] * 2 +
+                                 [c_u64, c_i32, c_i32, c_vp, c_vp, ctypes.POINTER(c_u64)]),
+        "gpue_hash_join_emit_build": (c_i32, [c_vp, c_vp, c_i32, c_vp, c_u64,
+                                              ctypes.POINTER(c_u64)]),
+        "gpue_hash_join_reset_marks": (c_i32, [c_vp, c_vp]),
+        "gpue_hash_join_destroy": (None, [c_vp]),
+        "gpue_gather_outer": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_i32, c_vp, c_u64, c_vp,
+                                      c_vp]),
         "gpue_sbf_build_i32": (c_i32, [c_vp, c_vp, c_u64, c_i32, c_vp]),
         "gpue_sbf_test_i32": (c_i32, [c_vp, c_vp, c_u64, c_vp, c_i32, c_vp]),
         "gpue_topk_i64": (c_i32, [c_vp, c_vp, c_vp, c_u64, c_i32, c_vp, c_vp]),
@@ -320,6 +334,16 @@ class AsofTable:
 class GroupAgg:
     """A general GROUP BY table (gpue_group_agg): the handle plus the layout
     it was created with (a groupagg.GroupAggSpec)."""
+
+    def __init__(self, eng: "Engine", handle, spec):
+        self._lib = eng._lib
+        self._h = handle
+        self.spec = spec
+
+
+class HashJoin:
+    """A general hash join table (gpue_hash_join): the handle plus the layout
+    it was created with (a hashjoin.HashJoinSpec)."""
 
     def __init__(self, eng: "Engine", handle, spec):
         self._lib = eng._lib
@@ -1080,6 +1104,154 @@ class Engine:
             return self.group_agg_emit_alloc(ga)
         finally:
             self.group_agg_destroy(ga)
+
+    # --- general hash join (gpue.h "general hash join") ---
+    HJ_INNER, HJ_LEFT_SEMI, HJ_LEFT_ANTI, HJ_LEFT_OUTER, HJ_NULL_AWARE_LEFT_ANTI, \
+        HJ_MARK_ONLY = range(6)
+    HJ_MARK_BUILD = 1
+    HJ_NO_ROW = 0xFFFFFFFF
+    HJ_MAX_KEYS = 4
+
+    def hash_join_create(self, build_types, probe_types, key_nullable, key_null_safe=None,
+                         capacity_hint=0) -> HashJoin:
+        """A persistent, growable join table over len(build_types) key columns
+        (PT_I32 / PT_I64 per side); the layout is fixed here. capacity_hint is
+        only a starting size."""
+        i32 = lambda xs: np.ascontiguousarray([int(x) for x in xs], np.int32)
+        if key_null_safe is None:
+            key_null_safe = [0] * len(build_types)
+        bt, pt, kn, ks = i32(build_types), i32(probe_types), i32(key_nullable), \
+            i32(key_null_safe)
+        h = c_vp()
+        _ck(self._lib, self._lib.gpue_hash_join_create(
+            self._h, bt.ctypes.data_as(c_vp), pt.ctypes.data_as(c_vp), kn.ctypes.data_as(c_vp),
+            ks.ctypes.data_as(c_vp), len(bt), capacity_hint, ctypes.byref(h)))
+        from starrocks_amd.hashjoin import HashJoinSpec
+        return HashJoin(self, h, HashJoinSpec(build_types, probe_types, key_nullable,
+                                              key_null_safe))
+
+    def hash_join_build_push(self, hj: HashJoin, keys, n_rows):
+        """keys = [(DBuf, nulls DBuf or None)] in the table's build layout.
+        The table copies them: the buffers may be freed on return."""
+        nk = len(keys)
+        _ck(self._lib, self._lib.gpue_hash_join_build_push(
+            self._h, hj._h, self._vp_array([k[0] for k in keys], nk),
+            self._vp_array([k[1] for k in keys], nk), n_rows))
+
+    def hash_join_build_rows(self, hj: HashJoin) -> int:
+        n = c_u64()
+        _ck(self._lib, self._lib.gpue_hash_join_build_rows(hj._h, ctypes.byref(n)))
+        return n.value
+
+    def hash_join_stats(self, hj: HashJoin) -> dict:
+        """slot capacity, distinct matchable tuples, doublings of the slot
+        array and re-insert passes so far."""
+        out = np.zeros(4, np.uint64)
+        _ck(self._lib, self._lib.gpue_hash_join_stats(hj._h, out.ctypes.data_as(c_vp)))
+        return dict(zip(("capacity", "distinct", "doublings", "rehashes"),
+                        (int(x) for x in out)))
+
+    def hash_join_probe(self, hj: HashJoin, keys, n_rows, mode, flags=0, out_probe=None,
+                        out_build=None) -> int:
+        """keys = [(DBuf, nulls DBuf or None)] in the probe layout. Without
+        outputs: the count only. Returns the pair count."""
+        nk = len(keys)
+        cnt = c_u64()
+        _ck(self._lib, self._lib.gpue_hash_join_probe(
+            self._h, hj._h, self._vp_array([k[0] for k in keys], nk),
+            self._vp_array([k[1] for k in keys], nk), n_rows, mode, flags,
+            out_probe._h if out_probe else None, out_build._h if out_build else None,
+            ctypes.byref(cnt)))
+        return cnt.value
+
+    def hash_join_emit_build(self, hj: HashJoin, matched, out: DBuf = None, max_out=0) -> int:
+        """The marked (matched=1) or unmarked (0) build rows, ascending.
+        Without out: the count only."""
+        cnt = c_u64()
+        _ck(self._lib, self._lib.gpue_hash_join_emit_build(
+            self._h, hj._h, matched, out._h if out else None, max_out, ctypes.byref(cnt)))
+        return cnt.value
+
+    def hash_join_reset_marks(self, hj: HashJoin):
+        _ck(self._lib, self._lib.gpue_hash_join_reset_marks(self._h, hj._h))
+
+    def hash_join_destroy(self, hj: HashJoin):
+        if hj._h:
+            self._lib.gpue_hash_join_destroy(hj._h)
+            hj._h = None
+
+    def hash_join_probe_alloc(self, hj: HashJoin, keys, n_rows, mode, flags=0):
+        """Count, then emit into exact-size outputs. Returns (probe_idx DBuf,
+        build_idx DBuf, n); freed on any exception."""
+        n = self.hash_join_probe(hj, keys, n_rows, mode, flags)
+        if mode == self.HJ_MARK_ONLY:
+            return self.alloc(4), self.alloc(4), 0
+        op, ob = self.alloc(max(n, 1) * 4), self.alloc(max(n, 1) * 4)
+        try:
+            if n:
+                # marking twice is idempotent, so the emit call keeps the flag off
+                got = self.hash_join_probe(hj, keys, n_rows, mode, 0, op, ob)
+                assert got == n
+        except BaseException:
+            op.free()
+            ob.free()
+            raise
+        return op, ob, n
+
+    def hash_join(self, build_keys, probe_keys, how, null_safe=None):
+        """One-shot join: build_keys / probe_keys = [(DBuf, nulls DBuf or
+        None, PT_I32 / PT_I64, n_rows)] per key (n_rows the same within a
+        side). how: inner, left_semi, left_anti, left_outer,
+        null_aware_left_anti, right_semi, right_anti, right_outer, full_outer.
+        Returns exact-size (probe_idx DBuf, build_idx DBuf, n) with the RIGHT /
+        FULL tail appended as (NO_ROW, b) rows; the inputs are left alone."""
+        from starrocks_amd import hashjoin as hjm
+        mode, flags, tail = hjm.plan(how)
+        nb, npr = build_keys[0][3], probe_keys[0][3]
+        spec = hjm.HashJoinSpec.of(build_keys, probe_keys, null_safe)
+        bk = [(k[0], k[1]) for k in build_keys]
+        pk = [(k[0], k[1]) for k in probe_keys]
+        spec.check_push(bk, nb)
+        spec.check_probe(pk, npr, mode, flags)
+        hj = self.hash_join_create(spec.build_types, spec.probe_types, spec.key_nullable,
+                                   spec.key_null_safe, nb)
+        bufs = []
+        try:
+            self.hash_join_build_push(hj, bk, nb)
+            op, ob, n = self.hash_join_probe_alloc(hj, pk, npr, mode, flags)
+            bufs += [op, ob]
+            if tail is None:
+                return op, ob, n
+            m = self.hash_join_emit_build(hj, tail)
+            fp, fb = self.alloc(max(n + m, 1) * 4), self.alloc(max(n + m, 1) * 4)
+            bufs += [fp, fb]
+            if n:
+                self.dbuf_d2d(op, fp, n * 4)
+                self.dbuf_d2d(ob, fb, n * 4)
+            if m:
+                fp.h2d(np.full(m, self.HJ_NO_ROW, np.uint32), n * 4)
+                tb = self.alloc(m * 4)
+                bufs.append(tb)
+                assert self.hash_join_emit_build(hj, tail, tb, m) == m
+                self.dbuf_d2d(tb, fb, m * 4, 0, n * 4)
+                tb.free()
+            op.free()
+            ob.free()
+            return fp, fb, n + m
+        except BaseException:
+            for b in bufs:
+                b.free()
+            raise
+        finally:
+            self.hash_join_destroy(hj)
+
+    def gather_outer(self, inp: DBuf, in_nulls, in_rows, width, idx: DBuf, n, out: DBuf,
+                     out_nulls=None):
+        """out[j] = in[idx[j]], or NULL (0, null byte 1) where idx[j] is
+        HJ_NO_ROW; in_nulls / out_nulls are DBufs or None."""
+        _ck(self._lib, self._lib.gpue_gather_outer(
+            self._h, inp._h, in_nulls._h if in_nulls else None, in_rows, width, idx._h, n,
+            out._h, out_nulls._h if out_nulls else None))
 
     def graph_capture(self, fn):
         """Capture fn()'s async launches as a hipGraph; returns the exec
